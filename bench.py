@@ -35,10 +35,8 @@ for p in (os.path.join(ROOT, "helix-db_amd"), os.path.join(ROOT, "oracle")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
-# HIP multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4); lanes that share one run back to back.
-# A serving host with several lanes raises it before the runtime starts; so does this harness.
-if not os.environ.get("HVX_BENCH_NO_HWQ"):  # (HVX_BENCH_NO_HWQ=1: leave it to the library's own default -- the A/B of INTEGRATION 3c)
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+# HIP multiplexes a process's streams onto a few hardware queues; lanes that share one run back to back.  main() loads the library
+# (hvx_runtime_prepare: at most 2 queues) before the runtime starts; a value the environment exports is kept.
 
 import numpy as np
 import torch
@@ -146,6 +144,8 @@ def parse():
                     help="distinct query batches the timed steps cycle through (0 = steps + warmup, at most 64): no two steps in flight "
                          "gather the same rows")
     ap.add_argument("--traffic-file", default=os.path.join(ROOT, "profiles", "traffic_latest.json"))
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the headline's timed steps, write what its last step returned (ids, scores, counts, status) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -353,6 +353,39 @@ def timed_steps(ls, qs, ef, steps, warmup, barrier):
     return elapsed, span, kms
 
 
+DUMP_LIMIT = 64 << 20  # bytes --dump-outputs may write in all
+
+
+def dump_outputs(ls, steps, out_dir):
+    """--dump-outputs: the answer of the LAST timed step, as its caller receives it (the merged lists when the corpus is sharded), from
+    the buffers of the lane that ran it -- nothing writes them between the timed steps and this call.  ids as float64 (exact below
+    2^53), scores / counts / status as float32, one DIR/<name>.npy each.  A batch too large for DUMP_LIMIT keeps a fixed sample of
+    its query rows (seed 0, in order), listed in rows.npy."""
+    l = (steps - 1) % len(ls.handles)
+    ls.sync()
+    if ls.groups:
+        ids, sc, cnt = ls.merged[l][:3]
+    elif ls.sharded:
+        sh = ls.sharded[l]
+        ids, sc, cnt = sh.m_ids, sh.m_scores, sh.m_counts
+    else:
+        ids, sc, cnt = ls.bufs[l][:3]
+    out = {"ids": ids.cpu().numpy().astype(np.float64), "scores": sc.cpu().numpy().astype(np.float32),
+           "counts": cnt.cpu().numpy().astype(np.float32), "status": ls.bufs[l][3].cpu().numpy().astype(np.float32)}
+    b = out["ids"].shape[0]
+    per_row = sum(a[:1].nbytes for a in out.values())
+    if b * per_row > DUMP_LIMIT:
+        keep = np.sort(np.random.default_rng(0).choice(b, size=(DUMP_LIMIT - 8 * b - 4096) // per_row, replace=False))
+        out = {name: a[keep] for name, a in out.items()}
+        out["rows"] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    info = {"dir": out_dir, "step": steps - 1, "lane": l, "arrays": {name: list(a.shape) for name, a in out.items()}}
+    log(f"outputs of the last timed step: {info}")
+    return info
+
+
 def hnsw_alg_bytes(qst, dim, elem, b):
     """distance_computations x dim x sizeof(elem) + neighbour-row ids examined x 4 B + the queries."""
     return int(qst[:, 3].sum()) * dim * elem + int(qst[:, 1].sum()) * 4 + b * dim * 4
@@ -380,7 +413,7 @@ def hnsw_leg(hv, synth, args, dev, dataset, n, dim, b, k, ef, dtype_name="f32", 
     ix = bix if bix is not None else import_index(hv, x, g, hv.EUCLIDEAN, hv.BF16 if bf16 else hv.F32, b, dev.index)
     lanes = max(1, args.lanes)
     occ = args.occupancy or (2 if lanes > 1 else 1)
-    # lanes BEFORE any other handle: HIP maps streams onto GPU_MAX_HW_QUEUES hardware queues (default 4) in creation order, and
+    # lanes BEFORE any other handle: HIP maps streams onto the process's hardware queues in creation order, and
     # two lanes that land on one queue run their kernels back to back (measured r03: 0.65 -> 0.44 ms/step on this leg)
     ls = LaneSet(ix, lanes, occ, b, k, dev)
     ix_truth = ix
@@ -1398,9 +1431,8 @@ def main():
     local_rank = 0 if SHARED_GPU else int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus and world == 1 and args.gpus > 1:
         raise SystemExit("launch with: python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...")
-    if os.environ.get("HVX_BENCH_NO_HWQ"):  # the library's load-time default must be in place before the HIP runtime initialises
-        import pyhvx
-        pyhvx.lib()
+    import pyhvx  # hvx_runtime_prepare (pyhvx.lib) must run before the HIP runtime initialises
+    pyhvx.lib()
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X (no CPU fallback exists for the product path)")
     torch.cuda.set_device(local_rank)
@@ -1418,6 +1450,8 @@ def main():
     hv.lib()
     skip = set(s for s in args.skip.split(",") if s)
 
+    if args.leg == "config5" and args.dump_outputs:
+        raise SystemExit("--dump-outputs writes the headline leg's answer; --leg config5 has none")
     if args.leg == "config5":
         res = run_config5_sharded(hv, synth, shard, args, dev, dist, rank, world)
         emit(res, args.full_record, rank)
@@ -1438,8 +1472,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def shard_run(n_total, label):
-        """One sharded (or single-GPU) measurement over a corpus of n_total rows; returns (result dict, state)."""
+    def shard_run(n_total, label, dump=False):
+        """One sharded (or single-GPU) measurement over a corpus of n_total rows; returns (result dict, state).  dump: write the
+        last timed step's answer under --dump-outputs."""
         t0 = time.time()
         n = n_total if replica else n_total // world
         nbq = query_batches(args, b)
@@ -1503,6 +1538,7 @@ def main():
             log(f"[{label}] host stall inside the timed steps ({stall}); timing the same {args.steps} steps again")
             elapsed, span, kms = timed_steps(ls, qs, ef, args.steps, args.warmup, barrier)
             timed_runs = 2
+        dumped = dump_outputs(ls, args.steps, args.dump_outputs) if dump and args.dump_outputs and rank == 0 else None
         q = ls.last_q[0]  # lane 0's last batch: recall, counters and the oracle check below refer to it
         if world > 1:
             t = torch.tensor([elapsed, span], dtype=torch.float64, device="cpu" if SHARED_GPU else dev)
@@ -1534,12 +1570,12 @@ def main():
         alg = hnsw_alg_bytes(qst, dim, 2 if bf16 else 4, b)
         per_step = span / args.steps
         res = dict(timed_runs=timed_runs, host_stall=stall, host_timing=getattr(ls, "host_timing", None), qps=qps, ms_per_step=elapsed * 1e3 / args.steps, recall=recall, alg=alg, per_step=per_step, kms=kms, qst=qst, n=n,
-                   n_total=n_total, flat_ms=flat_stats["device_ms"], graph=ginfo, exchange=exchange, nbq=nbq)
+                   n_total=n_total, flat_ms=flat_stats["device_ms"], graph=ginfo, exchange=exchange, nbq=nbq, dumped=dumped)
         state = dict(ix=ix, ix_truth=ix_truth, ls=ls, x=x, q=q, g=g, truth=f, id_lo=id_lo, qs=qs)
         return res, state
 
     n_weak_total = args.rows if replica else args.rows * world
-    res, S = shard_run(n_weak_total, "weak" if world > 1 else "1 GPU")
+    res, S = shard_run(n_weak_total, "weak" if world > 1 else "1 GPU", dump=True)
     ix, ls, q, g, x = S["ix"], S["ls"], S["q"], S["g"], S["x"]
     S_qs = S["qs"]
     headline_alive = True
@@ -1698,7 +1734,7 @@ def main():
         if not bf16 and "production" not in skip:
             prod = {}
             # the headline's forks are done (their buffers and last batches stay for the oracle check below): HIP maps streams onto
-            # GPU_MAX_HW_QUEUES = 8 hardware queues, and the lanes of the legs below must not share one with each other (r05a: the cosine
+            # the process's hardware queues, and the lanes of the legs below should not share one with each other (r05a: the cosine
             # lanes of this leg, created as streams 9-12 of the process, ran 1.7 kernels in flight instead of 2.6)
             ls.sync()
             for h in ls.handles[1:]:

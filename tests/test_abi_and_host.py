@@ -427,10 +427,11 @@ def test_link_workgroup_kernel_takes_its_row_locks_without_cache_maintenance(tmp
 
 
 def test_runtime_prepare_sets_the_hardware_queue_count_only_when_the_host_has_not():
-    """HIP maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4); execution lanes that share one run back to
+    """HIP maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues; execution lanes that share one run back to
     back (profiles/history/r04t_hw_queues_library_default.log: 0.69 instead of 0.80 of HBM on the headline, 0.51 instead of 0.67 on the bf16
     leg).  Round 5: LOADING the library no longer touches the environment; the host calls hvx_runtime_prepare(n) from its
-    start-up code, which sets the variable (0 = 8) unless the host has exported one itself."""
+    start-up code, which sets the variable (0 = 2) unless the host has exported one itself.  More than 2 is refused: a device's queue
+    slots are shared by every process on it."""
     import subprocess
     lib = os.path.join(ROOT, "helix-db_amd", "libhelix_vec_gfx950.so")
     if not os.path.exists(lib):
@@ -445,7 +446,7 @@ def test_runtime_prepare_sets_the_hardware_queue_count_only_when_the_host_has_no
             "rc = L.hvx_runtime_prepare(n) if n >= 0 else 0\n"
             "after = libc.getenv(b'GPU_MAX_HW_QUEUES')\n"
             "print(before.decode() if before else '-', after.decode() if after else '-', rc)\n")
-    for preset, n, want in (("", -1, "- - 0"), ("", 0, "- 8 0"), ("", 12, "- 12 0"), ("4", 0, "4 4 0"), ("16", 8, "16 16 0"), ("", 65, "- - 5")):
+    for preset, n, want in (("", -1, "- - 0"), ("", 0, "- 2 0"), ("", 1, "- 1 0"), ("1", 0, "1 1 0"), ("1", 2, "1 1 0"), ("", 3, "- - 5")):
         r = subprocess.run([sys.executable, "-c", code, lib, preset, str(n)], capture_output=True, text=True, timeout=120)
         assert r.returncode == 0 and r.stdout.strip() == want, (preset, n, r.stdout, r.stderr[-300:])
 
@@ -910,7 +911,7 @@ def test_bench_line_is_compact_strict_json_with_the_contract_keys():
                                             "score_bits_equal_oracle": True, "junk": "x" * 500} for m in ("l2", "cosine")}
     full["vendor_gemm"] = {"fp8": {"tflops": 2000.0}, "bf16": {"tflops": float("inf")}}
     full["batcher"]["qps_production_default"] = 1.0e6
-    line = bench.compact_record(full, "/root/repo/bench_full.json")
+    line = bench.compact_record(full, os.path.join(ROOT, "bench_full.json"))
     assert len(line) < bench.COMPACT_LIMIT == 4096 and "\n" not in line
     assert "NaN" not in line and "Infinity" not in line
     rec = json.loads(line, parse_constant=lambda c: (_ for _ in ()).throw(ValueError(c)))   # strict: NaN / Infinity tokens are rejected
@@ -932,7 +933,7 @@ def test_bench_line_is_compact_strict_json_with_the_contract_keys():
     # a record whose legs outgrow the budget sheds summaries, never the contract keys
     full["datasets"]["clustered"]["error"] = "y" * 5000
     full["config3_prefilter"]["groups"] = full["config3_prefilter"]["groups"] * 12
-    line2 = bench.compact_record(full, "/root/repo/bench_full.json")
+    line2 = bench.compact_record(full, os.path.join(ROOT, "bench_full.json"))
     rec2 = json.loads(line2)
     assert len(line2) < 4096 and rec2["value"] == full["value"] and "roofline" in rec2 and "cpu_baseline" in rec2
     # defaults are the driver's command
@@ -942,3 +943,50 @@ def test_bench_line_is_compact_strict_json_with_the_contract_keys():
     finally:
         sys.argv = argv
     assert (a.gpus, a.steps, a.warmup) == (1, 20, 5)
+
+
+def test_bench_dump_outputs_writes_the_last_timed_step(tmp_path, monkeypatch):
+    """bench.py --dump-outputs DIR: the answer of the LAST timed step (the lane that ran it), as float32 / float64 .npy files, the
+    same rows on every call; a batch above the size limit keeps a fixed sample of its query rows and lists them in rows.npy."""
+    import importlib.util
+    import torch
+    argv = sys.argv
+    sys.argv = ["bench.py"]
+    try:
+        spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+        bench = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(bench)
+        a = bench.parse()
+    finally:
+        sys.argv = argv
+    assert a.dump_outputs == ""
+
+    b, k = 96, 10
+
+    class Lanes:  # LaneSet's surface that dump_outputs reads: three lanes on one GPU
+        groups = sharded = None
+
+        def __init__(self):
+            self.handles = [None] * 3
+            self.bufs = [[torch.full((b, k), 1000 * l, dtype=torch.int64) + torch.arange(b * k).view(b, k),
+                          torch.full((b, k), 0.5 + l, dtype=torch.float32), torch.full((b,), k - l, dtype=torch.int32),
+                          torch.full((b,), l, dtype=torch.int32), torch.zeros(b, 4, dtype=torch.int32)] for l in range(3)]
+
+        def sync(self):
+            pass
+
+    info = bench.dump_outputs(Lanes(), 5, str(tmp_path / "a"))             # steps 0..4 on lanes 0,1,2,0,1: the last one ran on lane 1
+    assert info["lane"] == 1 and sorted(os.listdir(tmp_path / "a")) == ["counts.npy", "ids.npy", "scores.npy", "status.npy"]
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("ids", "scores", "counts", "status")}
+    assert got["ids"].dtype == np.float64 and all(got[n].dtype == np.float32 for n in ("scores", "counts", "status"))
+    assert np.array_equal(got["ids"], 1000 + np.arange(b * k, dtype=np.float64).reshape(b, k))
+    assert (got["scores"] == 1.5).all() and (got["counts"] == k - 1).all() and (got["status"] == 1).all()
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 4096 + 8 * b + 40 * (8 * k + 4 * k + 4 + 4))   # room for 40 of the 96 rows
+    for d in ("b", "c"):
+        bench.dump_outputs(Lanes(), 3, str(tmp_path / d))
+    rows = np.load(tmp_path / "b" / "rows.npy")
+    assert rows.shape == (40,) and (np.diff(rows) > 0).all() and np.array_equal(rows, np.load(tmp_path / "c" / "rows.npy"))
+    ids = np.load(tmp_path / "b" / "ids.npy")
+    assert np.array_equal(ids, 2000 + np.arange(b * k, dtype=np.float64).reshape(b, k)[rows.astype(np.int64)])   # step 2: lane 2
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= bench.DUMP_LIMIT
