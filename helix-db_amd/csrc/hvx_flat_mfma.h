@@ -46,6 +46,50 @@ hipError_t launch_flat_smallb(const MfmaArgs &a, int kind, bool full, uint32_t c
 hipError_t launch_flat_select_radix(const MfmaArgs &a, uint32_t kc, uint32_t *status, float *sl_sc, uint32_t *sl_id, uint32_t sl_stride,
                                     uint32_t *out_slices, hipStream_t s);
 
+// ---- the exact scan's error bound E: |approximate score - reference-order score| for every row, the ONE number the re-rank certificate
+// (hvx_flat_mfma.hip, rerank_bf16_kernel: kth < t - E) and the exact tail (hvx_flat_tail.hip: re-score iff s~ - E <= T) rest on ----
+// Contraction kinds: what the matrix cores multiplied.
+enum ScanErrKind : uint32_t {
+    kErrBf16OnePass,      // bf16 rows x the query's bf16 hi part
+    kErrBf16Full,         // bf16 rows x (hi + lo)
+    kErrF32ShadowOnePass, // f32 rows through their bf16 shadow (RNE) x hi
+    kErrF32RegOnePass,    // f32 rows rounded to bf16 (RNE) in registers x hi
+    kErrF32Full,          // f32 rows split hi + lo too: q_hi.x_hi + q_lo.x_hi + q_hi.x_lo
+    kErrFp8OnePass,       // fp8 codes widened to bf16 (exact; the row scale is applied in f32) x hi
+    kErrFp8Full,          // fp8 codes x (hi + lo)
+    kErrMxFp8,            // fp8 codes x the query as two e4m3 pieces (the MX-scaled 256 x 256 build)
+};
+
+// E relative to (|q|^2 + max |x|^2) / 2 for L2, absolute for cosine, at `dim` terms.  u = 2^-8 is bf16's unit roundoff: 8 significant
+// bits, so RNE moves a value by <= 2^-8 of it (half of 2^-7, the step of [1, 2)).  Per dot product the contraction is off by <= eps |q||x|:
+//   * one rounded operand (bf16 / fp8 rows x q_hi): |q - q_hi| <= u |q| per element, eps = u;
+//   * both rounded (f32 rows x q_hi, shadow or registers: both RNE): q_hi x_hi - q x = (q_hi - q) x_hi + q (x_hi - x), eps = 2u + u^2;
+//   * the hi + lo split of one value leaves r = v - hi - lo with |r| <= 2^-17 |v| (v - hi, |v - hi| <= 2^-8 2^e, rounded again: half a
+//     step of its binade, <= 2^-17 2^e <= 2^-17 |v|), so bf16 / fp8 rows x (hi + lo): eps = 2^-17; f32 rows with q_lo.x_lo dropped:
+//     r_q.x + q_hi.r_x + q_lo.x_lo + q_lo.r_x <= (2^-17 + 2^-17 (1 + u) + 2^-16 + 2^-25) |q||x| <= (2^-15 + 2^-23) |q||x|;
+//   * MX: hi = RNE(q / s) and lo = RNE(16 (q - s hi) / s) in e4m3 (3 mantissa bits): for q / s in [2^e, 2^e+1) the hi residual is <= 2^(e-4),
+//     lo lies below 2^e and rounds by <= 2^(e-5), i.e. 2^(e-9) of q / s -- |q - s hi - s lo / 16| <= 2^-9 |q| for normal pieces; a
+//     subnormal lo piece is off by <= 2^-10 s / 16 with s <= max |q| / 128 (split_queries_mx_kernel), i.e. <= 2^-21 max |q| per element,
+//     <= 2^-21 sqrt(dim) |q||x| summed against x.  eps = u + 2^-21 sqrt(dim): the normal pieces' term keeps u = 2^-8, twice their worst
+//     case (the value the MX build has used for L2 since it was added; tests/test_exact_bound_fixtures.py drives the error to 0.4-0.5 of the bound).
+// L2: s = |q|^2 + |x|^2 - 2 q.x moves by 2 eps |q||x| <= 2 eps (|q|^2 + |x|^2) / 2.  Cosine: s = (1 - c) / 2 with c = q.x / (|q||x|) moves by
+// eps / 2; the bound keeps eps, a factor two over that worst case (the value the cosine scan has always used).  Both add f32 accumulation
+// over dim terms in BOTH summation orders (6 dim 2^-24), doubled for whatever order the matrix core accumulates in, and 2^-18 for the f32
+// roundings of |q|^2, |x|^2 (f64 sums rounded once) and the few f32 operations of the epilogue.
+__host__ __device__ inline float scan_error_bound(uint32_t kind, bool l2, uint32_t dim) {
+    const float u = 0x1p-8f;
+    float eps;
+    switch (kind) {
+    case kErrBf16OnePass: case kErrFp8OnePass: eps = u; break;
+    case kErrBf16Full: case kErrFp8Full: eps = 0x1p-17f; break;
+    case kErrF32ShadowOnePass: case kErrF32RegOnePass: eps = 2.0f * u + u * u; break;
+    case kErrF32Full: eps = 0x1p-15f + 0x1p-23f; break;
+    case kErrMxFp8: eps = u + 0x1p-21f * sqrtf((float)dim); break;
+    default: eps = 1.0f; break; // (unknown kind: a bound that certifies nothing)
+    }
+    return (l2 ? 2.0f * eps : eps) + 12.0f * (float)dim * 0x1p-24f + 0x1p-18f;
+}
+
 // position of stored code `slot` (its index in the fp8 row) in the query operand of the 256 x 256 fp8 kernel: inside a
 // 64-code stage, MFMA step kk (0..3), lane half h, element e read code (2 (kk >> 1) + h) * 16 + (kk & 1) * 8 + e, so one
 // ds_read_b128 of the code tile feeds two steps.

@@ -4,7 +4,7 @@
 // Semantics are still restricted_exact_scan (crates/db/src/search/vector/restricted.rs:753-835): the k
 // smallest (score, id) pairs, scores produced by D::distance in the host kernel's summation order.  An
 // MFMA sums in a different order, so the pipeline is candidate generation + exact re-rank + certificate:
-//   1. queries are split into bf16 hi + lo parts (residual <= 2^-18 |q|) in the rows' interleaved layout
+//   1. queries are split into bf16 hi + lo parts (residual <= 2^-17 |q|) in the rows' interleaved layout
 //      (a dot product does not care about the permutation as long as both operands use it);
 //   2. `flat_mfma_bf16_kernel`: 128 queries x 128 rows per workgroup, v_mfma_f32_32x32x16_bf16,
 //      acc += q_hi.x + q_lo.x, epilogue turns the dot product into the metric's score and writes one
@@ -15,8 +15,8 @@
 //      summation order (the same gather/FMA code as the HNSW kernel), sorts by (score, id), keeps k;
 //   5. certificate: every row that was NOT re-scored has approximate score >= t (the (m+1)-th), hence a
 //      reference-order score >= t - E; if the k-th exact score is < t - E the answer is provably the
-//      exact scan's.  E bounds the bf16 split residual plus the f32 accumulation error of both orders
-//      (2e-5 + 12 dim 2^-24, relative to (|q|^2 + max|x|^2)/2 for L2, absolute for cosine).
+//      exact scan's.  E = scan_error_bound (hvx_flat_mfma.h): what the contraction's rounded operands leave out plus the f32
+//      accumulation error of both orders, relative to (|q|^2 + max|x|^2)/2 for L2, absolute for cosine.
 //      Queries that fail are re-run with m = 1023; if that fails too they are reported, never guessed.
 #include <hip/hip_runtime.h>
 
@@ -89,9 +89,9 @@ __global__ __launch_bounds__(64) void split_queries_kernel(const float *q, uint3
 
 // The query operand of the MX-scaled fp8 tile build (hvx_flat_tile.hip, flat_tile2mx_kernel): v_mfma_scale_f32_32x32x64_f8f6f4 multiplies
 // fp8 by fp8, so a query value is carried as TWO e4m3 pieces -- hi = RNE(q / s), lo = RNE((q - s hi) 16 / s), s = 2^E the power of two
-// that puts max |q| into (224, 448] -- and the instruction's block scales (E8M0: 127 + E for the hi piece, 4 less for the lo piece)
-// restore the magnitudes: q ~ s hi + (s / 16) lo with |q - that| <= 2^-8 |q| per element (3 mantissa bits twice; subnormal pieces add
-// <= 2^-18 max |q| absolute).  Layout: [query][dim / 64 stages][64 hi codes | 64 lo codes], element i at position fp8_slot_of(i) of the
+// that puts max |q| / s into [128, 256) -- and the instruction's block scales (E8M0: 127 + E for the hi piece, 4 less for the lo piece)
+// restore the magnitudes: q ~ s hi + (s / 16) lo with |q - that| <= 2^-9 |q| per element for normal pieces (3 mantissa bits twice; a
+// subnormal lo piece adds <= 2^-14 s <= 2^-21 max |q| absolute).  The certificate's bound: scan_error_bound(kErrMxFp8).  Layout: [query][dim / 64 stages][64 hi codes | 64 lo codes], element i at position fp8_slot_of(i) of the
 // row (the order the fp8 rows are stored in): a lane of the tile kernel reads 32 consecutive codes of a row and of a query.
 __global__ __launch_bounds__(64) void split_queries_mx_kernel(const float *q, uint32_t b, uint32_t bpad, uint32_t dim, unsigned char *qmx, uint32_t *qexp) {
     const uint32_t r = blockIdx.x;
@@ -129,9 +129,9 @@ constexpr int kLdsStride = kBK * 2 + 16;      // bytes per tile row: 64 B of dat
 
 
 // KIND: 0 = bf16 rows, 1 = fp8 rows, 2 = f32 rows (split into bf16 hi + lo on the way into LDS: acc += q_hi.x_hi +
-// q_lo.x_hi + q_hi.x_lo; the dropped q_lo.x_lo term is <= 2^-16 |q||x| and is covered by the certificate's bound).
-// FULL = false: the ONE-pass build -- only q_hi.x_hi; the dropped residual terms (<= 2^-9 |q||x| per rounded operand) are
-// added to the certificate's bound instead (RerankArgs::extra_rel), queries that then fail it are repeated with FULL.
+// q_lo.x_hi + q_hi.x_lo; the dropped q_lo.x_lo term is <= 2^-16 |q||x| and is covered by the certificate's bound, kErrF32Full).
+// FULL = false: the ONE-pass build -- only q_hi.x_hi; the dropped residual terms (<= 2^-8 |q||x| per rounded operand: bf16's unit
+// roundoff) are in the certificate's bound instead (scan_error_bound), queries that then fail it are repeated with FULL.
 // FILT = true: the score matrix is not written; a score leaves the tile only if it is below the query's running threshold.
 template <int KIND, bool FULL, bool FILT>
 __global__ __launch_bounds__(256) void flat_mfma_bf16_kernel(MfmaArgs a) {
@@ -410,7 +410,7 @@ struct RerankArgs {
     const uint32_t *cand_counts; // [b]
     uint32_t kc, k, m;        // kc = m + 1 slots; results k
     float xmax2;              // max |x|^2 over the rows
-    float extra_rel;          // added to the certificate's relative bound: the residual terms a one-pass contraction dropped
+    float erel;               // the certificate's bound E: scan_error_bound of the contraction that produced the candidates
     uint64_t *out_ids;
     float *out_scores;
     uint32_t *out_counts, *out_status;
@@ -642,12 +642,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         uint32_t ok = 1u;
         if (nc > a.m) {
             const float t = t_thr;
-            // worst-case |approximate - reference-order score| relative to (|q|^2 + |x|^2)/2 (L2) resp. absolute (cosine):
-            // hi/lo split residuals (<= 2^-17 each way, the dropped lo.lo term and the f32 roundings of the norms:
-            // 2e-5 in all) + f32 accumulation over K = dim terms in BOTH summation orders (6 K 2^-24 worst case),
-            // the latter doubled for whatever order the matrix core accumulates in.  K = 1536 -> 1.1e-3, K = 128 -> 1.1e-4.
-            const float erel = 2.0e-5f + 12.0f * (float)(NK * 32) * 5.9604645e-8f + a.extra_rel;
-            const float e = METRIC == kL2 ? erel * 0.5f * (a.qn2[q] + a.xmax2) : erel;
+            // worst-case |approximate - reference-order score| relative to (|q|^2 + |x|^2)/2 (L2) resp. absolute (cosine)
+            const float e = METRIC == kL2 ? a.erel * 0.5f * (a.qn2[q] + a.xmax2) : a.erel;
             const float kth = outn ? ss[outn - 1] : inf;
             ok = (outn == a.k && kth < t - e) ? 1u : 0u;
         }
@@ -671,6 +667,14 @@ static hipError_t launch_rerank(const RerankArgs &a, uint32_t b, hipStream_t s) 
     }
     return hipGetLastError();
 }
+
+} // namespace hvx
+
+// scan_error_bound evaluated by the host compiler, for the CPU tests that hold the bound to its numpy twin and to the adversarial fixtures
+// (tests/test_exact_bound_fixtures.py).  Not part of the C ABI (include/helix_vec.h).
+extern "C" float hvxi_scan_error_bound(uint32_t kind, uint32_t l2, uint32_t dim) { return hvx::scan_error_bound(kind, l2 != 0u, dim); }
+
+namespace hvx {
 
 hipError_t launch_bf16_row_norm2(const uint16_t *rows, uint32_t n, uint32_t dim, float *out, hipStream_t s) {
     if (n == 0) return hipSuccess;
@@ -895,8 +899,8 @@ static int flat_mfma_impl(hvx_index *ix, const float *d_queries, uint32_t b, uin
                 // round 6: the approximate dot products become the exact answer in ONE more launch (hvx_flat_tail.hip): rows whose
                 // approximate score could be below the query's k-th exact score are re-scored in the reference's order -- no candidate
                 // count, no certificate, nothing to read back, never a second pass over the rows
-                const float dropped = f32 ? 0.0078125f : 0.00390625f; // what the one-pass contraction left out (RerankArgs::extra_rel)
-                if ((rc = flat_tail_enqueue(ix, d_queries, b, k, ix->f_dist, chunk, n, d_subset, ma.rowterm, ix->m_qn2, dropped, d_ids, d_scores, d_counts, d_status))) return rc;
+                const float erel = scan_error_bound(f32 ? (sb_kind == 0 ? kErrF32ShadowOnePass : kErrF32RegOnePass) : kErrBf16OnePass, d.metric == kL2, d.dim);
+                if ((rc = flat_tail_enqueue(ix, d_queries, b, k, ix->f_dist, chunk, n, d_subset, ma.rowterm, ix->m_qn2, erel, d_ids, d_scores, d_counts, d_status))) return rc;
                 if (timed) HIP_TRY(hipEventRecord(ix->ev1, ix->stream));
                 ix->last_scan_path |= HVX_PATH_SMALL_BATCH | HVX_PATH_EXACT_TAIL;
                 return HVX_OK;
@@ -953,11 +957,13 @@ static int flat_mfma_impl(hvx_index *ix, const float *d_queries, uint32_t b, uin
         ra.cert = ix->m_cert;
         ra.sl_sc = nullptr; ra.sl_id = nullptr; ra.sl_n = 0; ra.sl_stride = 0;
         if (smallb && sb_radix) { ra.sl_sc = ix->m_csc; ra.sl_id = ix->m_cid; ra.sl_n = sb_slices * kc; ra.sl_stride = kSmallbCandCap; }
-        // one rounded operand drops a term <= 2^-9 |q||x| of the dot product = 2^-8 of (|q|^2 + |x|^2)/2 in the L2 score
-        // (cosine: <= 2^-10 absolute); f32 rows round BOTH operands in the one-pass build
-        ra.extra_rel = full ? 0.f : (f32 ? 0.0078125f : 0.00390625f);
-        // the MX build's query is two e4m3 pieces: |q - q^| <= 2^-8 |q| per element (+ subnormal pieces: 2^-18 max |q|) -- twice the bf16 hi part's
-        if (used_mx) ra.extra_rel = 0.0079f;
+        // the bound of the contraction that produced the candidates: f32 rows round BOTH operands in the one-pass build (the bf16
+        // shadow or in registers); a one-pass scan that used the MX build for some slices takes its (larger) bound for all
+        const uint32_t err_kind = full ? (f32 ? kErrF32Full : (fp8 ? kErrFp8Full : kErrBf16Full))
+                                       : used_mx ? kErrMxFp8
+                                       : f32 ? ((used_tile || (smallb && sb_kind == 0)) ? kErrF32ShadowOnePass : kErrF32RegOnePass)
+                                       : (fp8 ? kErrFp8OnePass : kErrBf16OnePass);
+        ra.erel = scan_error_bound(err_kind, d.metric == kL2, d.dim);
         HIP_TRY(d.metric == kL2 ? launch_rerank<kL2>(ra, b, ix->stream) : launch_rerank<kCosine>(ra, b, ix->stream));
         if (timed) HIP_TRY(hipEventRecord(ix->ev1, ix->stream));
         if ((rc = ix->pin_flags((size_t)b + 1))) return rc; // read back through pinned memory: a pageable copy is a synchronous staged one

@@ -42,7 +42,7 @@ __device__ __forceinline__ uint32_t pack_bf16(float lo, float hi) {
 
 // KIND 0: bf16 rows (a bf16 index, or the bf16 shadow of an f32 index), 2: f32 rows.  NQT: 32-query tiles held in LDS.
 // FULL: the hi + lo split (acc += q_hi.x_hi + q_lo.x_hi [+ q_hi.x_lo for f32 rows]; the dropped lo.lo term is covered by the
-// certificate's bound) -- false = the one-pass build (q_hi.x_hi only, RerankArgs::extra_rel widens the bound).
+// certificate's bound) -- false = the one-pass build (q_hi.x_hi only, scan_error_bound (hvx_flat_mfma.h) widens the bound).
 // WAVES: wavefronts per workgroup = per CU (the query tiles fill most of the LDS).  U: MFMA steps (16 deep) per register group.
 // Output = the raw dot products [b][rows] in a.dist (the selection kernel below turns them into scores).  The query tiles of
 // one workgroup must fit the LDS: when they do not (dim 1536 with the lo tile) the depth is split over gridDim.y workgroup

@@ -11,8 +11,9 @@
 // score (one atomicMin word), and re-scores -- in the reference's summation order, on the reference's f32 / bf16 values -- every row whose
 // approximate score could be below it:  s~ - E <= T,  E = the contraction's worst-case error (the bound the certificate used).
 //   * a row of the true top-k has  s <= (k-th smallest exact score) <= T  and  s~ - E <= s : it passes the filter and is re-scored.  Every
-//     other row either fails the filter or loses in the exact list.  No approximate number ever reaches the result: exact by construction,
-//     for ANY error bound -- a loose bound (one rounded pass over bf16 shadows) only re-scores more rows;
+//     other row either fails the filter or loses in the exact list.  No approximate number ever reaches the result: exact by construction
+//     for any E that really bounds |s~ - s| (scan_error_bound, hvx_flat_mfma.h) -- a loose bound only re-scores more rows, one below the
+//     contraction's rounding can drop a true top-k row with status 0 (tests/test_gpu_exact_bounds.py);
 //   * T starts at +inf.  A workgroup = (query, slice of 4 096 scores) bounds the k-th smallest exact score of its slice WITHOUT touching a
 //     row -- k rows with approximate score <= t have exact score <= t + E; t = the k-th smallest of a wavefront's 64 lane minima (one
 //     shuffle sort) -- publishes t + E (atomicMin), reads back the minimum over all workgroups so far, filters its 4 096 scores once and
@@ -52,7 +53,7 @@ struct TailArgs {
     uint32_t chunk_ld, rows;
     const uint32_t *subset;   // scan position -> row, or NULL
     const float *rowterm;     // [n] |x|^2 (L2) / |x| (cosine)
-    float xmax2, erel;        // max |x|^2; relative error bound of the contraction (absolute for cosine)
+    float xmax2, erel;        // max |x|^2; scan_error_bound of the contraction (relative for L2, absolute for cosine)
     uint32_t b, k, slices;
     uint32_t *thr;            // [b] bits of the smallest k-th exact score published so far (+inf between launches)
     float *part_sc;           // [b][slices][k]
@@ -155,7 +156,7 @@ __global__ __launch_bounds__(256) void flat_exact_tail_kernel(TailArgs a) {
         // ---- the slice's approximate scores ----
         const float *dq = a.dots + (size_t)q * a.chunk_ld;
         const float qn2 = a.qn2[q], qn = sqrtf(qn2);
-        // worst-case |approximate - reference-order score| (hvx_flat_mfma.hip, rerank_bf16_kernel: the certificate's bound)
+        // worst-case |approximate - reference-order score| (scan_error_bound: the certificate's bound)
         const float E = METRIC == kL2 ? a.erel * 0.5f * (qn2 + a.xmax2) : a.erel;
         float as[kTailR];
         uint32_t an[kTailR];
@@ -337,8 +338,8 @@ bool flat_tail_supported(const hvx_index *ix, uint32_t b, uint32_t k, uint32_t n
     return d.dtype == HVX_BF16;
 }
 
-// `dots` = the approximate dot products [b][chunk_ld] of `rows` scan positions (hvx_flat_smallb.hip); erel as RerankArgs::extra_rel + the
-// split's own bound.  Writes the exact top-k of every query; nothing is read back.
+// `dots` = the approximate dot products [b][chunk_ld] of `rows` scan positions (hvx_flat_smallb.hip); erel = scan_error_bound of the
+// contraction that produced them (hvx_flat_mfma.h).  Writes the exact top-k of every query; nothing is read back.
 int flat_tail_enqueue(hvx_index *ix, const float *d_queries, uint32_t b, uint32_t k, const float *dots, uint32_t chunk_ld, uint32_t rows,
                       const uint32_t *d_subset, const float *rowterm, const float *qn2, float erel, uint64_t *d_ids, float *d_scores,
                       uint32_t *d_counts, uint32_t *d_status) {
@@ -363,10 +364,7 @@ int flat_tail_enqueue(hvx_index *ix, const float *d_queries, uint32_t b, uint32_
     a.queries = d_queries; a.qstatus = ix->d_qstatus; a.qhdr = ix->d_qhdr; a.qn2 = qn2;
     a.dots = dots; a.chunk_ld = chunk_ld; a.rows = rows; a.subset = d_subset; a.rowterm = rowterm;
     a.xmax2 = ix->m_xmax2;
-    // worst-case |approximate - reference-order score| relative to (|q|^2 + |x|^2) / 2 (L2), absolute (cosine): the certificate's bound
-    // (hvx_flat_mfma.hip rerank_bf16_kernel) -- split residuals 2e-5 + f32 accumulation in both orders 12 K 2^-24 + what a one-pass
-    // contraction dropped
-    a.erel = 2.0e-5f + 12.0f * (float)d.dim * 5.9604645e-8f + erel;
+    a.erel = erel;
     a.b = b; a.k = k; a.slices = slices;
     a.bad = ix->t_ctl; a.done = ix->t_ctl + ix->cap_t_ctl; a.thr = ix->t_ctl + (size_t)ix->cap_t_ctl * 2;
     a.part_sc = ix->t_part_sc; a.part_row = ix->t_part_row;

@@ -155,3 +155,248 @@ def quantize_fp8_rows(x: np.ndarray) -> np.ndarray:
     v = np.minimum(v, np.float32(448.0))
     v = np.where(y < 0, -v, v).astype(np.float32)
     return (scale[:, None] * v).astype(np.float32)
+
+
+# ---- adversarial rounding for the matrix-core exact scan (hvx_flat_mfma.h, scan_error_bound) ----
+# The one-pass contraction rounds the query to bf16 (and f32 rows too); the exact tail (hvx_flat_tail.hip) and the re-rank
+# certificate (hvx_flat_mfma.hip) are exact only if E bounds |approximate - reference-order score|.  Gaussian rows let the
+# per-element rounding errors cancel; these rows line every error up with the same sign.
+
+# contraction kinds of scan_error_bound (same order as the C++ enum)
+ERR_BF16_ONE_PASS, ERR_BF16_FULL, ERR_F32_SHADOW_ONE_PASS, ERR_F32_REG_ONE_PASS, ERR_F32_FULL, ERR_FP8_ONE_PASS, ERR_FP8_FULL, ERR_MX_FP8 = range(8)
+
+
+def scan_error_bound(kind: int, l2: bool, dim: int) -> float:
+    """numpy twin of hvx::scan_error_bound: relative to (|q|^2 + max|x|^2) / 2 for L2, absolute for cosine."""
+    u = 2.0 ** -8
+    eps = {ERR_BF16_ONE_PASS: u, ERR_FP8_ONE_PASS: u, ERR_BF16_FULL: 2.0 ** -17, ERR_FP8_FULL: 2.0 ** -17,
+           ERR_F32_SHADOW_ONE_PASS: 2 * u + u * u, ERR_F32_REG_ONE_PASS: 2 * u + u * u, ERR_F32_FULL: 2.0 ** -15 + 2.0 ** -23,
+           ERR_MX_FP8: u + 2.0 ** -21 * math.sqrt(dim)}[kind]
+    return (2.0 * eps if l2 else eps) + 12.0 * dim * 2.0 ** -24 + 2.0 ** -18
+
+
+def scan_error_bound_before_fix(one_pass: bool, f32_rows: bool, l2: bool, dim: int) -> float:
+    """the bound the library used before it was derived per kind (RerankArgs::extra_rel): one rounded operand taken to
+    drop <= 2^-9 |q||x|, which under-states bf16's 2^-8 unit roundoff"""
+    extra = (2.0 ** -7 if f32_rows else 2.0 ** -8) if one_pass else 0.0
+    return 2.0e-5 + 12.0 * dim * 2.0 ** -24 + extra
+
+
+def _f32(x) -> np.ndarray:
+    return np.asarray(x, np.float32)
+
+
+def _halves(dim: int):
+    h = dim // 2
+    return np.arange(h), np.arange(h, dim)
+
+
+def adversarial_query(dim: int) -> np.ndarray:
+    """half the elements at 1 + 2^-8 - 2^-20 (bf16 RNE rounds them DOWN by almost 2^-8), half at 1 + 2^-8 + 2^-20 (rounded UP)"""
+    A, B = _halves(dim)
+    q = np.empty(dim, np.float32)
+    q[A] = 1.0 + 2.0 ** -8 - 2.0 ** -20
+    q[B] = 1.0 + 2.0 ** -8 + 2.0 ** -20
+    return q
+
+
+FP8_ROW_MAX = 448.0 / 256.0  # 1.75
+
+
+def adversarial_query_mx(dim: int) -> np.ndarray:
+    """the MX build's trap (split_queries_mx_kernel: s = 2^-6 here, max |q| / s in [128, 256)): q / s = 132.25 -+ 2^-10, so hi = 128 and
+    lo = RNE(16 (4.25 -+ 2^-10)) = 64 resp. 72 in e4m3 (step 8 at [64, 128)): half the elements rounded DOWN by (0.25 - 2^-10) s, half
+    UP by as much -- 2^-9.05 of |q|, the two-piece split's worst case for normal pieces"""
+    A, B = _halves(dim)
+    q = np.empty(dim, np.float32)
+    q[A] = (132.25 - 2.0 ** -10) * 2.0 ** -6
+    q[B] = (132.25 + 2.0 ** -10) * 2.0 ** -6
+    return q
+
+
+def e4m3_rne(y) -> np.ndarray:
+    """f64 -> the nearest e4m3fn value (ties to even, saturating at 448): fp8_e4m3_encode / decode of hvx_device.h"""
+    y = np.asarray(y, np.float64)
+    a = np.minimum(np.abs(y), 448.0)
+    e = np.floor(np.log2(np.where(a > 0, a, 1.0)))
+    e = np.where((a == 0) | (e < -6), -6.0, e)
+    step = np.exp2(e - 3)
+    v = np.minimum(np.rint(a / step) * step, 448.0)
+    return np.where(y < 0, -v, v)
+
+
+def mx_query(q: np.ndarray) -> np.ndarray:
+    """f64 model of split_queries_mx_kernel: the value the MX build multiplies, s hi + (s / 16) lo"""
+    q = _f32(q)
+    mx = float(np.abs(q).max())
+    e = (math.frexp(mx)[1] - 8) if mx > 0 else 0
+    s = 2.0 ** e
+    hi = e4m3_rne(q.astype(np.float64) / s)
+    res = q.astype(np.float64) - hi * s
+    lo = e4m3_rne(res / s * 16.0)
+    return s * hi + s / 16.0 * lo
+
+
+def adversarial_pair(dim: int, rows: str, nudge: float = 1.0 / 16.0):
+    """(r, t) for adversarial_query: r's one-pass score is pushed UP by the rounding, its mirror t's DOWN, by as much as the
+    rounding can; one element of r is nudged toward the query so that r is the exact nearest (L2 and cosine).  rows: "bf16"
+    (values exact in bf16: only the query rounds) or "f32" (the rows round too, in the same direction)."""
+    A, B = _halves(dim)
+    q = adversarial_query(dim)
+    r = np.empty(dim, np.float32)
+    t = np.empty(dim, np.float32)
+    if rows == "bf16":
+        r[A], r[B] = 2.0, -2.0
+        t[A], t[B] = -2.0, 2.0
+    elif rows == "fp8":  # +-448 x 2^-8: the row scale max|x| / 448 is 2^-8, every value an e4m3 code point; the nudge is one code step
+        r[A], r[B] = FP8_ROW_MAX, -FP8_ROW_MAX
+        t[A], t[B] = -FP8_ROW_MAX, FP8_ROW_MAX
+        r[B[0]] = -416.0 / 256.0
+        return _f32(r), _f32(t)
+    else:  # |x| = 2 q: x rounds in the direction its query element does
+        r[A], r[B] = 2.0 * q[A], -2.0 * q[B]
+        t[A], t[B] = -2.0 * q[A], 2.0 * q[B]
+    r[B[0]] += np.float32(nudge)
+    return _f32(r), _f32(t)
+
+
+def far_rows(n: int, dim: int, rng, rows: str) -> np.ndarray:
+    """rows far from the adversarial queries (every element in -[1.5, 1.99], fp8: -[1.3, 1.74] quantised) whose norms stay below the
+    fixture's: max |x|^2 -- and with it E -- is the adversarial rows' own"""
+    if rows == "fp8":
+        return quantize_fp8_rows((-rng.uniform(1.3, 1.74, (n, dim))).astype(np.float32))
+    x = (-rng.uniform(1.5, 1.99, (n, dim))).astype(np.float32)
+    return round_bf16(x) if rows == "bf16" else x
+
+
+def one_pass_scores(metric: int, data: np.ndarray, q: np.ndarray, rows: str, full: bool = False, mx: bool = False) -> np.ndarray:
+    """f64 model of the matrix-core scores of every row: the dot product of the bf16-RNE query (+ its lo part when full) with the
+    rows as the contraction sees them (bf16 rows as stored; f32 rows bf16-RNE, + their lo parts when full), turned into the
+    metric's score with the exact norms the kernels use (|q|^2, |x|^2 in f64 rounded to f32; cosine: (1 - c) / 2).  fp8 rows: the stored
+    values (codes widened exactly, the row scale applied after); mx: the query as the MX build's two e4m3 pieces (mx_query)."""
+    q = _f32(q)
+    x = _f32(data).astype(np.float64)
+    qh = mx_query(q) if mx else round_bf16(q).astype(np.float64)
+    ql = 0.0 if mx else round_bf16(_f32(q - round_bf16(q))).astype(np.float64)
+    if rows == "f32":
+        xh = round_bf16(_f32(data)).astype(np.float64)
+        xl = round_bf16(_f32(_f32(data) - round_bf16(_f32(data)))).astype(np.float64)
+        dot = xh @ qh + ((xh @ ql + xl @ qh) if full else 0.0)
+    else:
+        dot = x @ (qh + (ql if full else 0.0))
+    qn2 = float(np.float32((q.astype(np.float64) ** 2).sum()))
+    xn2 = (x ** 2).sum(axis=1).astype(np.float32).astype(np.float64)
+    if metric == 1:
+        return np.maximum(qn2 + xn2 - 2.0 * dot, 0.0)
+    c = np.clip(dot / (math.sqrt(qn2) * np.sqrt(xn2)), -1.0, 1.0)
+    return (1.0 - c) * 0.5
+
+
+def exact_scores(metric: int, data: np.ndarray, q: np.ndarray) -> np.ndarray:
+    """the scores in f64 on the stored values (the oracle's f32 scores are within its accumulation error of these)"""
+    x = _f32(data).astype(np.float64)
+    qd = _f32(q).astype(np.float64)
+    if metric == 1:
+        return ((x - qd) ** 2).sum(axis=1)
+    return (1.0 - (x @ qd) / (np.linalg.norm(x, axis=1) * np.linalg.norm(qd))) * 0.5
+
+
+def error_scale(metric: int, data: np.ndarray, q: np.ndarray) -> float:
+    """what the relative L2 bound multiplies: (|q|^2 + max|x|^2) / 2; 1 for cosine's absolute bound"""
+    if metric != 1:
+        return 1.0
+    return 0.5 * (float((_f32(q).astype(np.float64) ** 2).sum()) + float((_f32(data).astype(np.float64) ** 2).sum(axis=1).max()))
+
+
+def tail_fixture(dim: int, rows: str, k: int, n_far: int, seed: int):
+    """the exact tail's trap: r (the exact nearest, at a random position) and k copies of its mirror t among n_far far rows.  With an
+    E below the rounding, the tail publishes t's approximate score + E as the k-th bound and never re-scores r.
+    Returns (stored rows, query, r's position, t positions)."""
+    rng = np.random.default_rng(seed)
+    r, t = adversarial_pair(dim, rows)
+    n = n_far + 1 + k
+    data = far_rows(n, dim, rng, rows)
+    # the t's at consecutive positions from a multiple of 64: distinct lanes of ONE wavefront of the tail, whose k-th smallest lane
+    # minimum is then t's score (scattered copies leave a far row's score there, and the bound never gets tight)
+    t0 = 64 * int(rng.integers(0, (n - k) // 64))
+    tp = list(range(t0, t0 + k))
+    rp = int(rng.choice(np.setdiff1d(np.arange(n), tp)))
+    data[tp] = t
+    data[rp] = r
+    return data, adversarial_query(dim), rp, tp
+
+
+def fp8_filler_row(dim: int, q: np.ndarray, target: float) -> np.ndarray:
+    """filler_row for fp8 rows: values on the e4m3 code points of the row scale 2^-8 (one pair at -1.75 sets that scale), equal within
+    each pair (one element per query half: the query's rounding errors cancel), chosen pair by pair to bring the score to the target"""
+    A, B = _halves(dim)
+    qd = _f32(q).astype(np.float64)
+    codes = np.unique(np.abs(e4m3_rne(np.linspace(0.0, 448.0, 20000))))
+    grid = -codes * 2.0 ** -8
+    x = np.full(dim, -(1.0 / 256.0) * float(e4m3_rne(256.0 * (float(qd.mean()) - math.sqrt(target / dim)))), np.float64)
+    x = -np.abs(x)
+    x[A[0]] = x[B[0]] = -FP8_ROW_MAX
+    for sweep in range(3):  # nearest first, then from above
+        for j in range(1, len(A)):
+            others = ((qd - x) ** 2).sum() - (qd[A[j]] - x[A[j]]) ** 2 - (qd[B[j]] - x[B[j]]) ** 2
+            f = others + (qd[A[j]] - grid) ** 2 + (qd[B[j]] - grid) ** 2
+            ok = f >= target if sweep == 2 else np.ones(f.shape, bool)
+            v = grid[ok][np.argmin(np.abs(f[ok] - target))] if ok.any() else grid[np.argmax(f)]
+            x[A[j]] = x[B[j]] = v
+    assert ((qd - x) ** 2).sum() >= target
+    return _f32(x)
+
+
+def filler_row(dim: int, q: np.ndarray, target: float) -> np.ndarray:
+    """a row of bf16 values whose one-pass L2 score is EXACT up to accumulation (equal sums over the two query halves: the
+    query's rounding errors cancel) and lies in [target, target + a few bf16 steps): -c everywhere, then pairs (one element per
+    half) one bf16 step further from the query until the score reaches the target"""
+    A, B = _halves(dim)
+    qd = _f32(q).astype(np.float64)
+    c = 1.0 - math.sqrt(target / dim)  # (q - c)^2 = target / dim with q ~ 1
+    x = np.full(dim, round_bf16(_f32([c]))[0], np.float32)
+    step = np.float32(2.0 ** -7)  # the bf16 step of values in [1, 2)
+    while ((qd - x) ** 2).sum() >= target:  # start below the target
+        x = round_bf16(x + step)
+    for j in range(len(A) * 4):
+        if ((qd - x) ** 2).sum() >= target:
+            break
+        x[A[j % len(A)]] -= step
+        x[B[j % len(A)]] -= step
+    assert ((qd - x) ** 2).sum() >= target
+    return round_bf16(x)
+
+
+def certificate_fixture(dim: int, rows: str, k: int, m: int, n_far: int, seed: int, mx: bool = False, min_pos: int = 0):
+    """the re-rank certificate's trap: k copies of t (approximations pushed down), m + 1 - k fillers with accurate approximations just
+    above them, and r (the exact nearest) whose approximation overshoots past the fillers: the m + 1 candidates are the t's and the
+    fillers, and r is row m + 2.  The certificate must fail (k-th exact score = t's is not below (m+1)-th approximate - E)
+    with an honest E; an E below the rounding certifies the t's -- a wrong answer.
+    The fillers sit above t's exact score by more than `e_trap`: the library's bound before scan_error_bound (bf16 / f32 / fp8 rows),
+    a quarter of scan_error_bound for the MX build (mx=True: its query, adversarial_query_mx, and rows from position min_pos on, past the
+    first chunk that the bf16 query scores).
+    Returns (stored rows, query, r's position, t positions, filler positions)."""
+    rng = np.random.default_rng(seed)
+    r, t = adversarial_pair(dim, rows)
+    q = adversarial_query_mx(dim) if mx else adversarial_query(dim)
+    pair = np.stack([r, t])
+    s_ex = exact_scores(1, pair, q)
+    s_ap = one_pass_scores(1, pair, q, rows, mx=mx)
+    lo, hi = s_ex[1] + certificate_trap_bound(rows, dim, mx) * error_scale(1, pair, q), s_ap[0]
+    target = lo + 0.25 * (hi - lo)
+    f = fp8_filler_row(dim, q, target) if rows == "fp8" else filler_row(dim, q, target)
+    nf = m + 1 - k
+    n = n_far + 1 + k + nf
+    data = far_rows(n, dim, rng, rows)
+    pos = min_pos + rng.permutation(n - min_pos)
+    data[pos[0]] = r
+    data[pos[1:k + 1]] = t
+    data[pos[k + 1:k + 1 + nf]] = f
+    return data, q, int(pos[0]), [int(p) for p in pos[1:k + 1]], [int(p) for p in pos[k + 1:k + 1 + nf]]
+
+
+def certificate_trap_bound(rows: str, dim: int, mx: bool) -> float:
+    """the bound the certificate fixture is built to defeat (relative, L2)"""
+    if mx:
+        return 0.25 * scan_error_bound(ERR_MX_FP8, True, dim)
+    return scan_error_bound_before_fix(True, rows == "f32", True, dim)
