@@ -24,7 +24,6 @@
 //                             layer's workgroups, the last workgroup replays select_diverse from registers; NARROW (rows <= 34 ids) and
 //                             WIDE (rows <= 64 ids: M 32 / M0 64 graphs) builds, f32 and bf16 rows.  The relinks happen IN ORDER (a relink
 //                             reads rows earlier relinks of the same delete changed): one step after the other on the stream
-//   delete_step_own / _recip  the same step as two launches (HVX_OPT_DELETE_SEQUENTIAL = 2)
 //   delete_relink_kernel      one wavefront per layer: empties x's own rows and sets its deleted bit; with HVX_OPT_DELETE_SEQUENTIAL = 1
 //                             it also runs every relink itself (lazy select_diverse: the round-5 first build, 26.9 ms per delete)
 // A deleted node keeps its row slot: unreachable (nothing links to it, the entry point is repaired), absent from every id -> row
@@ -60,8 +59,6 @@ constexpr uint32_t kDelRelCap = 4096;   // relink sources per layer (sorted in L
 constexpr uint32_t kDelCandCap = 16384; // candidates per layer (one source's scores live in LDS)
 constexpr uint32_t kDelTop = 64;        // Mmax (round 6: degree limits up to 64 through the wide build of the fused step)
 constexpr uint32_t kDelMinLayers = 16;
-constexpr uint32_t kDelWaves = 4;  // wavefronts of a step workgroup (32 row groups of 8 lanes)
-constexpr uint32_t kDelDm = 65 * 64; // one prune's distance matrix
 
 struct DeleteArgs {
     DevIndex ix;
@@ -74,10 +71,9 @@ struct DeleteArgs {
     uint32_t *cand, *cand_cnt; // [layers][kDelCandCap], [layers]
     uint32_t *top, *top_cnt;   // [layers][kDelRelCap][kDelTop], [layers][kDelRelCap]: a source's closest candidates, Candidate order
     uint32_t *mark;            // [layers][words] all zero between kernels
-    uint32_t *newl, *new_cnt;  // [layers][kDelTop], [layers]: the neighbours the current step's source has gained (step kernels)
-    float *gdm;                // [layers][1 + kDelTop][65 x 64]: the distance matrices of a step's prunes (slot 0: the source's own row,
-    uint32_t *tick;            //  1 + t: its t-th new neighbour's), and per matrix the workgroups that have delivered (zero between launches)
-    uint32_t g_own, g_recip;   // workgroups that share one matrix
+    float *gdm;                // [layers][fuse_layer_dm]: the distance matrices of a step's prunes (the source's own row, then its candidates')
+    uint32_t *tick;            // [layers]: the workgroups of a layer that have delivered their share of a step (zero between launches)
+    uint32_t g_own, g_recip;   // workgroups of a step on layer 0 / on every upper layer
     uint32_t first;            // delete_relink_kernel starts with this source (the ones before it ran as steps)
     uint32_t *dead;            // the image's deleted-row bitmap
     uint32_t *ctl;             // [0] error (1 sources, 2 relink sources, 3 candidates, 4 invalid score, 5 row overflow) [1] relinked rows
@@ -357,257 +353,23 @@ template <uint32_t METRIC, bool FUSED> __global__ __launch_bounds__(64) void del
     }
 }
 
-
 // ---------------------------------------------------------------------------------------------------------------------------------
-// The same relinks as STEPS (the default): the one-wavefront kernel below evaluates every prune lazily -- candidate after candidate, each a
+// The same relinks as STEPS (the default): the one-wavefront kernel above evaluates every prune lazily -- candidate after candidate, each a
 // dependent row gather -- ~0.5 ms per prune and ~15 prunes per source (26.9 ms per delete at 200 000 x 768, profiles/r05t_delete_bench.json).
-// A step runs one source: delete_step_own_kernel (one 16-wavefront workgroup per layer) merges the source's row with its closest
-// candidates and, beyond Mmax, evaluates the WHOLE distance matrix of the <= 64 ids at once (every wavefront stages one id's vector and
-// scores it against all the others, reference summation order) before one wavefront replays select_diverse + backfill from LDS;
-// delete_step_recip_kernel (one workgroup per new neighbour) does the same for the reciprocal rows, which are independent of each
-// other.  Same distances, same comparisons, same order of decisions as the lazy evaluation: the rows are identical (both modes are
-// held to the oracle by tests/test_gpu_delete.py; HVX_OPT_DELETE_SEQUENTIAL selects the one-wavefront kernel).
+// A step runs one source in ONE launch (round 6) and evaluates the WHOLE distance matrix of every prune at once (reference summation
+// order) before select_diverse + backfill are replayed from it.  The reciprocal rows' matrices do not have to wait for the source's
+// prune -- the neighbours a source can gain are known before it (its closest candidates that its row does not hold: the prune only
+// decides which of them stay), and their rows do not change during the step until their own reciprocal update.  So every workgroup of a
+// layer derives the same task list -- task 0: the source's merged row, task t: "candidate t's row + the source" --, the pairs of ALL
+// tasks are spread over the layer's workgroups (one 8-lane group per pair), and the LAST workgroup to deliver replays the prunes from
+// LDS: wavefront 0 the source's, then sixteen wavefronts the reciprocal rows of the candidates that stayed.  A matrix is SYMMETRIC bit for
+// bit -- (a - b)^2 = (b - a)^2, a b = b a, |a - b| = |b - a|, and the cosine finish is symmetric in its two norms -- so only the pairs
+// i > j are evaluated and each is stored twice.  One launch and one ticket
+// per relinked row (the retired two-launch build took up to 33 tickets: 37 us per step -> see profiles/r06n_*).  Same distances, same
+// comparisons, same order of decisions as the lazy evaluation: the rows are identical (both modes are held to the oracle by
+// tests/test_gpu_delete.py; HVX_OPT_DELETE_SEQUENTIAL = 1 selects the one-wavefront kernel).
 // (A pair distance that is not a valid score aborts the reference only if select_diverse reaches that pair; the eager matrix treats
 // it as "not closer" -- rows validated at import cannot produce one under the component limit.)
-// ---------------------------------------------------------------------------------------------------------------------------------
-struct StepLds {
-    float *Dm;                                // [65][64]: Dm[i][j] = distance(staged id i, stored id j); row nc = the owner
-    uint32_t *cur, *ord, *sel, *kept, *oldl;  // [64] each
-    float *osc;                               // [64]
-    uint32_t *misc;                           // [8]
-};
-__device__ __forceinline__ StepLds carve_step(char *smem) {
-    StepLds S;
-    char *p = smem;
-    S.Dm = reinterpret_cast<float *>(p); p += 65 * 64 * 4;
-    S.cur = reinterpret_cast<uint32_t *>(p); p += 256;
-    S.ord = reinterpret_cast<uint32_t *>(p); p += 256;
-    S.sel = reinterpret_cast<uint32_t *>(p); p += 256;
-    S.kept = reinterpret_cast<uint32_t *>(p); p += 256;
-    S.oldl = reinterpret_cast<uint32_t *>(p); p += 256;
-    S.osc = reinterpret_cast<float *>(p); p += 256;
-    S.misc = reinterpret_cast<uint32_t *>(p);
-    return S;
-}
-static size_t step_lds_bytes() { return (size_t)kDelDm * 4 + 6 * 256 + 64; }
-
-
-__device__ __forceinline__ void store_canonical_wave(uint32_t *row, uint32_t stride, const uint32_t *ids_lds, uint32_t ns, uint32_t lane) {
-    const uint32_t mine = lane < ns ? ids_lds[lane] : kSentinel;
-    uint32_t rank = 0;
-    for (uint32_t s = 0; s < ns; ++s) rank += ids_lds[s] < mine ? 1u : 0u;
-    for (uint32_t t = lane; t < stride; t += 64u)
-        if (t >= ns) st_row(row + t, kSentinel);
-    if (lane < ns) st_row(row + rank, mine);
-}
-
-// S.cur[0..nc) pruned to at most maxn ids around `owner` (prune_row_dev's result, evaluated eagerly): S.kept[0..return).
-// G workgroups share the prune: every one of them evaluates its share of the distance matrix into gdm; the LAST one to deliver (one
-// relaxed fetch-add behind a workgroup-scope release, hvx_restricted_exact.hip) loads the matrix and replays select_diverse -- the
-// others get kSentinel back and leave.
-template <uint32_t METRIC, bool FUSED>
-__device__ __forceinline__ uint32_t prune_eager(const DevIndex &ix, const StepLds &S, uint32_t owner, uint32_t nc, uint32_t maxn, uint32_t tid, uint32_t g,
-                                                uint32_t G, float *gdm, uint32_t *tick, bool *bad) {
-    const uint32_t wave = tid >> 6, lane = tid & 63u;
-    const int j = (int)(lane & 7u);
-    // Round 6: the matrix is SYMMETRIC bit for bit -- (a - b)^2 = (b - a)^2, a b = b a, |a - b| = |b - a|, and the cosine finish is symmetric
-    // in its two norms -- so only the pairs i > j are evaluated, each by one 8-lane group with BOTH rows read in place (the "query" row
-    // through the same pointer arithmetic as a staged copy: the same operands in the same order).  One workgroup evaluating all <= 2 080
-    // pairs pulls 12.5 MB through ONE compute unit's vector cache: 48 - 51 us per step kernel, 2 ms of a 2.6-ms delete (rounds 3-5 and the
-    // first build of this round).  Spread over G workgroups of 32 row groups every group has about one pair: the matrix costs one row gather.
-    __syncthreads();
-    const uint32_t npairs = (nc + 1u) * nc / 2u;
-    for (uint32_t p = g * (kDelWaves * 8u) + (tid >> 3); p < npairs; p += G * (kDelWaves * 8u)) {
-        // p = i (i - 1) / 2 + jj, 0 <= jj < i <= nc
-        uint32_t i = (uint32_t)((1.0f + sqrtf(1.0f + 8.0f * (float)p)) * 0.5f);
-        while (i * (i - 1u) / 2u > p) --i;
-        while ((i + 1u) * i / 2u <= p) ++i;
-        const uint32_t jj = p - i * (i - 1u) / 2u;
-        const uint32_t node_i = i < nc ? S.cur[i] : owner, node_j = S.cur[jj];
-        const float d = group_distance<METRIC, FUSED>(ix, ix.vec + (size_t)node_i * ix.ld, ix.hdr[node_i], node_j, j);
-        if (j == 0) {
-            st_agent(gdm + i * 64u + jj, d);
-            if (i < nc) st_agent(gdm + jj * 64u + i, d);
-        }
-    }
-    stores_done(); // the stores have been acknowledged before the ticket is taken
-    __syncthreads();
-    if (tid == 0) S.misc[1] = __hip_atomic_fetch_add(tick, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == G ? 1u : 0u;
-    __syncthreads();
-    if (!S.misc[1]) return kSentinel;
-    if (tid == 0) st_agent(tick, 0u); // (the next launch starts from zero)
-    for (uint32_t t = tid; t < (nc + 1u) * 64u; t += kDelWaves * 64u) S.Dm[t] = ld_agent(gdm + t); // (the diagonal is never read)
-    __syncthreads();
-    if (wave == 0) {
-        const float dmine = lane < nc ? S.Dm[nc * 64u + lane] : 0.f;
-        const uint32_t v = lane < nc ? S.cur[lane] : kSentinel;
-        float chk = dmine;
-        if (__ballot(lane < nc && !score_valid(chk)) != 0ull) *bad = true;
-        uint32_t rank = 0;
-        for (uint32_t t = 0; t < nc; ++t) { // Candidate order: score, then id
-            const float dt = S.Dm[nc * 64u + t];
-            const uint32_t idt = S.cur[t];
-            rank += (dt < dmine || (dt == dmine && idt < v)) ? 1u : 0u;
-        }
-        if (lane < nc) { S.ord[rank] = lane; S.osc[rank] = dmine; }
-        lds_order();
-        // select_diverse (mod.rs:822-842): strict < rejects.  The ranked candidates and the selection live in REGISTERS (lane r holds
-        // the r-th candidate and its score, lane l the l-th selected one): a step is two lane broadcasts, one LDS gather of the matrix and a
-        // ballot -- no LDS write + fence per accepted candidate
-        const uint32_t my_ord = lane < nc ? S.ord[lane] : 0u;
-        const float my_osc = lane < nc ? S.osc[lane] : 0.f;
-        uint32_t my_sel = 0u; // the index (into S.cur) of the lane-th selected candidate
-        uint32_t ns = 0;
-        for (uint32_t r = 0; r < nc && ns < maxn; ++r) {
-            const uint32_t ci = (uint32_t)__builtin_amdgcn_readlane((int)my_ord, (int)r);
-            const float sc = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(my_osc), (int)r));
-            const bool closer = lane < ns && S.Dm[ci * 64u + my_sel] < sc;
-            if (__ballot(closer) == 0ull) {
-                if (lane == ns) my_sel = ci;
-                ++ns;
-            }
-        }
-        if (lane < ns) S.sel[lane] = my_sel;
-        lds_order();
-        if (ns < maxn) { // backfill, closest first (mod.rs:845-854)
-            const bool have = lane < nc;
-            const uint32_t mine = have ? my_ord : kSentinel;
-            bool in = false;
-            for (uint32_t s = 0; s < ns; ++s) in |= S.sel[s] == mine;
-            const unsigned long long fm = __ballot(have && !in);
-            const uint32_t rk = (uint32_t)__builtin_popcountll(fm & ((1ull << lane) - 1ull));
-            if (have && !in && ns + rk < maxn) S.sel[ns + rk] = mine;
-            const uint32_t add = (uint32_t)__builtin_popcountll(fm);
-            ns = ns + add < maxn ? ns + add : maxn;
-            lds_order();
-        }
-        if (lane < ns) S.kept[lane] = S.cur[S.sel[lane]];
-        if (lane == 0) S.misc[0] = ns;
-    }
-    __syncthreads();
-    return S.misc[0];
-}
-
-// relink_neighbor (mutation.rs:1916-1993) for source `ri` of every layer: merge, prune, stage; the neighbours it has gained go to newl.
-// grid (layers, g_own): every workgroup of a layer reads the same row and closest-candidate list and arrives at the same merged row;
-// without a prune workgroup 0 finishes alone, with one the last workgroup to deliver its share of the matrix does
-template <uint32_t METRIC, bool FUSED> __global__ __launch_bounds__(256) void delete_step_own_kernel(DeleteArgs a, uint32_t ri) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    __shared__ uint32_t s_go, s_ncur, s_nold;
-    const DevIndex &ix = a.ix;
-    const uint32_t L = blockIdx.x, g = blockIdx.y, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
-    const StepLds S = carve_step(smem);
-    if (tid == 0) s_go = (a.ctl[0] == 0u && ri < a.rel_cnt[L]) ? 1u : 0u;
-    __syncthreads();
-    if (!s_go) { if (g == 0u && tid == 0) a.new_cnt[L] = 0; return; }
-    const uint32_t nb = a.rel[(size_t)L * kDelRelCap + ri];
-    const uint32_t maxn = L == 0u ? a.m0 : a.m;
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    uint32_t stride;
-    uint32_t *row = del_row(a, nb, L, stride);
-    if (wave == 0) {
-        const uint32_t v = lane < stride ? ld_row(row + lane) : kSentinel;
-        const uint32_t nold = (uint32_t)__builtin_popcountll(__ballot(v != kSentinel));
-        const uint32_t tn = a.top_cnt[(size_t)L * kDelRelCap + ri];
-        const uint32_t tv = lane < tn ? a.top[((size_t)L * kDelRelCap + ri) * kDelTop + lane] : kSentinel;
-        S.oldl[lane] = v;
-        lds_order();
-        bool in_old = false;
-        for (uint32_t s = 0; s < nold; ++s) in_old |= S.oldl[s] == tv;
-        const bool add = tv != kSentinel && !in_old;
-        const unsigned long long am = __ballot(add);
-        const uint32_t ncur = nold + (uint32_t)__builtin_popcountll(am);
-        if (ncur <= 64u) {
-            if (lane < nold) S.cur[lane] = v;
-            if (add) S.cur[nold + (uint32_t)__builtin_popcountll(am & lt)] = tv;
-        }
-        if (lane == 0) { s_ncur = ncur; s_nold = nold; }
-    }
-    __syncthreads();
-    const uint32_t ncur = s_ncur, nold = s_nold;
-    if (ncur > 64u) { if (g == 0u && tid == 0) { a.new_cnt[L] = 0; atomicMax(&a.ctl[0], 5u); } return; }
-    bool bad = false;
-    uint32_t keepn = ncur;
-    if (ncur > maxn) {
-        keepn = prune_eager<METRIC, FUSED>(ix, S, nb, ncur, maxn, tid, g, a.g_own, a.gdm + (size_t)L * (1u + kDelTop) * kDelDm, a.tick + L * (1u + kDelTop), &bad);
-        if (keepn == kSentinel) return;
-    } else {
-        if (g != 0u) return;
-        if (wave == 0 && lane < ncur) S.kept[lane] = S.cur[lane];
-        __syncthreads();
-    }
-    if (wave == 0) {
-        const uint32_t f = lane < keepn ? S.kept[lane] : kSentinel;
-        bool was_old = false;
-        for (uint32_t s = 0; s < nold; ++s) was_old |= S.oldl[s] == f;
-        const bool isnew = f != kSentinel && !was_old;
-        const unsigned long long nm = __ballot(isnew);
-        if (keepn > stride) { if (lane == 0) { a.new_cnt[L] = 0; atomicMax(&a.ctl[0], 5u); } return; }
-        store_canonical_wave(row, stride, S.kept, keepn, lane);
-        if (isnew) a.newl[(size_t)L * kDelTop + (uint32_t)__builtin_popcountll(nm & lt)] = f;
-        if (lane == 0) {
-            a.new_cnt[L] = (uint32_t)__builtin_popcountll(nm);
-            if (bad) atomicMax(&a.ctl[0], 4u);
-        }
-    }
-}
-
-// ... and the reciprocal row of each of them (mutation.rs:1994-2052): g_recip workgroups per new neighbour (grid x = neighbour x g_recip)
-template <uint32_t METRIC, bool FUSED> __global__ __launch_bounds__(256) void delete_step_recip_kernel(DeleteArgs a, uint32_t ri) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    __shared__ uint32_t s_go, s_rdeg, s_has;
-    const DevIndex &ix = a.ix;
-    const uint32_t L = blockIdx.y, bx = blockIdx.x / a.g_recip, g = blockIdx.x % a.g_recip, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
-    const StepLds S = carve_step(smem);
-    if (tid == 0) s_go = (a.ctl[0] == 0u && ri < a.rel_cnt[L] && bx < a.new_cnt[L]) ? 1u : 0u;
-    __syncthreads();
-    if (!s_go) return;
-    const uint32_t nb = a.rel[(size_t)L * kDelRelCap + ri], nw = a.newl[(size_t)L * kDelTop + bx];
-    const uint32_t maxn = L == 0u ? a.m0 : a.m;
-    uint32_t rstride;
-    uint32_t *rrow = del_row(a, nw, L, rstride);
-    if (wave == 0) {
-        uint32_t rv = lane < rstride ? ld_row(rrow + lane) : kSentinel;
-        uint32_t rdeg = (uint32_t)__builtin_popcountll(__ballot(rv != kSentinel));
-        const bool has = __ballot(rv == nb) != 0ull;
-        if (!has && rdeg < 64u) {
-            if (lane == rdeg) rv = nb;
-            ++rdeg;
-            if (lane < rdeg) S.cur[lane] = rv;
-        } else if (!has) {
-            rdeg = 65u;
-        }
-        if (lane == 0) { s_rdeg = rdeg; s_has = has ? 1u : 0u; }
-    }
-    __syncthreads();
-    if (s_has) return;
-    const uint32_t rdeg = s_rdeg;
-    if (rdeg > 64u) { if (g == 0u && tid == 0) atomicMax(&a.ctl[0], 5u); return; }
-    bool bad = false;
-    uint32_t kn = rdeg;
-    if (rdeg > maxn) {
-        kn = prune_eager<METRIC, FUSED>(ix, S, nw, rdeg, maxn, tid, g, a.g_recip, a.gdm + ((size_t)L * (1u + kDelTop) + 1u + bx) * kDelDm,
-                                        a.tick + L * (1u + kDelTop) + 1u + bx, &bad);
-        if (kn == kSentinel) return;
-    } else {
-        if (g != 0u) return;
-        if (wave == 0 && lane < rdeg) S.kept[lane] = S.cur[lane];
-        __syncthreads();
-    }
-    if (wave == 0) {
-        if (kn <= rstride) store_canonical_wave(rrow, rstride, S.kept, kn, lane);
-        if (lane == 0 && (bad || kn > rstride)) atomicMax(&a.ctl[0], bad ? 4u : 5u);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------------
-// A step as ONE launch (round 6): the reciprocal rows' matrices do not have to wait
-// for the source's prune -- the neighbours a source can gain are known before it (its closest candidates that its row does not hold: the
-// prune only decides which of them stay), and their rows do not change during the step until their own reciprocal update.  So every
-// workgroup of a layer derives the same task list -- task 0: the source's merged row, task t: "candidate t's row + the source" --, the
-// pairs of ALL tasks are spread over the layer's workgroups (one 8-lane group per pair), and the LAST workgroup to deliver replays the
-// prunes from LDS: wavefront 0 the source's, then sixteen wavefronts the reciprocal rows of the candidates that stayed.  One launch and one
-// ticket per relinked row instead of two launches and up to 33 tickets (37 us per step -> see profiles/r06n_*).
 // ---------------------------------------------------------------------------------------------------------------------------------
 constexpr uint32_t kFuseWaves = 16;
 // NARROW: rows of at most 34 ids (degree limits <= 32 on canonical rows): a source's merged row <= 64 ids, a reciprocal list <= 35 -- one
@@ -845,14 +607,14 @@ __global__ __launch_bounds__(256) void delete_best_entry_kernel(DevIndex ix, con
 
 using DeleteKernel = void (*)(DeleteArgs);
 using DeleteStepKernel = void (*)(DeleteArgs, uint32_t);
-struct DeleteKernels { DeleteKernel rank, relink; DeleteStepKernel own, recip, fused, fused_wide; };
+struct DeleteKernels { DeleteKernel rank, relink; DeleteStepKernel fused, fused_wide; };
 template <uint32_t METRIC, bool FUSED> static DeleteKernels delete_kernels_of() {
-    return {delete_rank_kernel<METRIC, FUSED, false>, delete_relink_kernel<METRIC, FUSED>, delete_step_own_kernel<METRIC, FUSED>, delete_step_recip_kernel<METRIC, FUSED>,
-            delete_step_fused_kernel<METRIC, FUSED, false, false>, delete_step_fused_kernel<METRIC, FUSED, false, true>};
+    return {delete_rank_kernel<METRIC, FUSED, false>, delete_relink_kernel<METRIC, FUSED>, delete_step_fused_kernel<METRIC, FUSED, false, false>,
+            delete_step_fused_kernel<METRIC, FUSED, false, true>};
 }
 // bf16 images: the ranking and the fused steps read the interleaved rows (the one-wavefront kernel only retires the node there)
 template <uint32_t METRIC> static DeleteKernels delete_kernels_bf16() {
-    return {delete_rank_kernel<METRIC, true, true>, delete_relink_kernel<METRIC, true>, nullptr, nullptr, delete_step_fused_kernel<METRIC, true, true, false>,
+    return {delete_rank_kernel<METRIC, true, true>, delete_relink_kernel<METRIC, true>, delete_step_fused_kernel<METRIC, true, true, false>,
             delete_step_fused_kernel<METRIC, true, true, true>};
 }
 static DeleteKernels pick_delete_kernels(uint32_t metric, bool fused, bool bf16) {
@@ -893,8 +655,8 @@ extern "C" int hvx_index_delete_batch(hvx_index *ix, const uint64_t *node_ids, u
     const uint32_t layers_now = d.max_layer + 1u;
     if (!ix->del_scratch || ix->del_layers < layers_now) {
         const uint32_t layers = std::max(kDelMinLayers, layers_now);
-        const size_t per_layer = ((size_t)kDelSrcCap + kDelRelCap + kDelCandCap + (size_t)kDelRelCap * kDelTop + kDelRelCap + words + 4u + kDelTop +
-                                  std::max<size_t>((size_t)(1u + kDelTop) * (kDelDm + 1u), (size_t)fuse_layer_dm<FuseT<true>>() + 2u + kDelTop)) * 4u;
+        const size_t per_layer = ((size_t)kDelSrcCap + kDelRelCap + kDelCandCap + (size_t)kDelRelCap * kDelTop + kDelRelCap + words + 3u +
+                                  fuse_layer_dm<FuseT<true>>() + 1u) * 4u;
         void *p = nullptr;
         if ((rc = ix->dalloc(&p, per_layer * layers + 64))) return rc;
         HIP_TRY(hipMemsetAsync(p, 0, per_layer * layers + 64, s));
@@ -909,15 +671,13 @@ extern "C" int hvx_index_delete_batch(hvx_index *ix, const uint64_t *node_ids, u
         a.src_cnt = p; p += layers;
         a.rel_cnt = p; p += layers;
         a.cand_cnt = p; p += layers;
-        a.new_cnt = p; p += layers;
-        a.newl = p; p += (size_t)layers * kDelTop;
         a.src = p; p += (size_t)layers * kDelSrcCap;
         a.rel = p; p += (size_t)layers * kDelRelCap;
         a.cand = p; p += (size_t)layers * kDelCandCap;
         a.top_cnt = p; p += (size_t)layers * kDelRelCap;
         a.top = p; p += (size_t)layers * kDelRelCap * kDelTop;
-        a.gdm = reinterpret_cast<float *>(p); p += (size_t)layers * std::max<size_t>((size_t)(1u + kDelTop) * kDelDm, fuse_layer_dm<FuseT<true>>());
-        a.tick = p; p += (size_t)layers * (1u + kDelTop);
+        a.gdm = reinterpret_cast<float *>(p); p += (size_t)layers * fuse_layer_dm<FuseT<true>>();
+        a.tick = p; p += layers;
         a.mark = p;
     }
     a.l0 = const_cast<uint32_t *>(d.l0);
@@ -930,30 +690,21 @@ extern "C" int hvx_index_delete_batch(hvx_index *ix, const uint64_t *node_ids, u
     const size_t relink_lds = (((size_t)d.ld * 4u + 15u) & ~(size_t)15u) + 4 * 256 + 256;
     if (rank_lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)kern.rank, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rank_lds));
     if (relink_lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)kern.relink, hipFuncAttributeMaxDynamicSharedMemorySize, (int)relink_lds));
-    const size_t step_lds = step_lds_bytes();
-    const bool steps = ix->opt[HVX_OPT_DELETE_SEQUENTIAL] != 1u;
-    // one launch per step while a reciprocal list (row + the source) fits the fused kernel's LDS matrices; HVX_OPT_DELETE_SEQUENTIAL = 2
-    // keeps the two-launch steps (A/B, and what wider rows take)
+    const bool steps = ix->opt[HVX_OPT_DELETE_SEQUENTIAL] != 1u; // (1: the one-wavefront kernel relinks every source itself)
+    // the narrow build of the step while a reciprocal list (row + the source) fits one candidate per lane, the wide build for rows of up to 64 ids
     const bool narrow = d.s0 + 1u <= FuseT<false>::ROWMAX && d.su + 1u <= FuseT<false>::ROWMAX && m0 <= 32u && m <= 32u;
-    const bool fused_steps = steps && (ix->opt[HVX_OPT_DELETE_SEQUENTIAL] != 2u || !narrow); // (rows of up to 64 ids: the wide build of the fused step)
-    if (bf16 && !fused_steps)
+    if (bf16 && !steps)
         return fail(HVX_ERR_UNSUPPORTED, "a bf16 image relinks by fused steps only (HVX_OPT_DELETE_SEQUENTIAL unset)");
-    if (!narrow && !fused_steps)
+    if (!narrow && !steps)
         return fail(HVX_ERR_UNSUPPORTED, "rows wider than 34 ids / degree limits above 32 relink by fused steps only (HVX_OPT_DELETE_SEQUENTIAL unset)");
     const DeleteStepKernel fused_kernel = narrow ? kern.fused : kern.fused_wide;
     const size_t fused_lds = narrow ? fuse_lds_bytes<FuseT<false>>() : fuse_lds_bytes<FuseT<true>>();
-    const uint32_t groups = kDelWaves * 8u;
-    if (fused_steps) {
+    if (steps) {
         // workgroups (128 row groups each) of layer 0 / of every upper layer: a typical step has ~8 000 pairs on layer 0 (the source's
         // <= 2 080 and ~10 reciprocal lists of 561), at most 20 032; the wide build: <= 8 256 + 64 x 2 145
         a.g_own = narrow ? 96u : 192u;
         a.g_recip = narrow ? 12u : 24u;
         HIP_TRY(hipFuncSetAttribute((const void *)fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused_lds));
-    } else {
-        // workgroups (32 row groups each) that share one prune's distance matrix: about one pair per row group.  A source's row grows to
-        // at most 64 ids (65 x 64 / 2 pairs), a reciprocal row to Mmax + 1
-        a.g_own = (65u * 64u / 2u + groups - 1u) / groups;
-        a.g_recip = ((m0 + 2u) * (m0 + 1u) / 2u + groups - 1u) / groups;
     }
     a.first = steps ? kDelRelCap : 0u; // every source runs as a step (their number is read back below); the one-wavefront kernel only retires the node
     // this generation's deleted-row flags: a copy of the visible ones (forks keep theirs until hvx_index_refresh)
@@ -993,14 +744,8 @@ extern "C" int hvx_index_delete_batch(hvx_index *ix, const uint64_t *node_ids, u
             for (uint32_t l = 0; l < a.layers; ++l) most = std::max(most, ix->h_flags[4 + l]);
             n_steps = std::min(kDelRelCap, most);
         }
-        for (uint32_t ri = 0; steps && ri < n_steps; ++ri) { // (a step past a layer's last source returns at once)
-            if (fused_steps) {
-                hipLaunchKernelGGL(fused_kernel, dim3(a.g_own + (a.layers - 1u) * a.g_recip), dim3(kFuseWaves * 64u), fused_lds, s, a, ri);
-                continue;
-            }
-            hipLaunchKernelGGL(kern.own, dim3(a.layers, a.g_own), dim3(kDelWaves * 64u), step_lds, s, a, ri);
-            hipLaunchKernelGGL(kern.recip, dim3(kDelTop * a.g_recip, a.layers), dim3(kDelWaves * 64u), step_lds, s, a, ri);
-        }
+        for (uint32_t ri = 0; steps && ri < n_steps; ++ri) // (a step past a layer's last source returns at once)
+            hipLaunchKernelGGL(fused_kernel, dim3(a.g_own + (a.layers - 1u) * a.g_recip), dim3(kFuseWaves * 64u), fused_lds, s, a, ri);
         hipLaunchKernelGGL(kern.relink, dim3(a.layers), dim3(64), relink_lds, s, a);
         HIP_TRY(hipGetLastError());
         (*flags)[row] = 1;
@@ -1025,7 +770,7 @@ extern "C" int hvx_index_delete_batch(hvx_index *ix, const uint64_t *node_ids, u
         static const char *why[] = {"", "more than 4096 rows hold one node on a layer", "more than 4096 relink sources on a layer", "more than 16384 relink candidates on a layer",
                                     "a distance is not a valid score (Candidate::try_new fails: the reference aborts the delete)", "a neighbour row overflowed its stride"};
         const uint32_t code = c4[0] < 6u ? c4[0] : 5u;
-        (void)hipMemsetAsync(ix->del_scratch, 0, 64 + (size_t)ix->del_layers * 4u * 4u, s); // counters; the marks of an aborted layer may be dirty:
+        (void)hipMemsetAsync(ix->del_scratch, 0, 64 + (size_t)ix->del_layers * 3u * 4u, s); // counters; the marks of an aborted layer may be dirty:
         ix->del_scratch = nullptr;                                                           // ... the next call starts from fresh scratch
         ix->del_layers = 0;
         return fail(code == 4u ? HVX_ERR_INVARIANT : HVX_ERR_UNSUPPORTED, "device delete: %s -- the image is partially relinked: discard the handle and hydrate again", why[code]);

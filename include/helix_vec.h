@@ -146,15 +146,15 @@ enum hvx_option {
     HVX_OPT_FLAT_NO_FILTER = 5,      /* 1: no filtered epilogue (every chunk writes its score matrix) */
     HVX_OPT_FLAT_NO_FAST = 6,        /* 1: start with the full hi + lo split */
     HVX_OPT_FLAT_TILE_BUILD = 7,     /* large-tile kernel: 0 = two 256-thread workgroups per CU (256 x 128 tiles), fp8 rows on the MX-scaled fp8
-                                        matrix instruction (query as two e4m3 pieces); 1 = one 512-thread workgroup (256 x 256); 2 = 512 threads
-                                        role-split; 3 = as 0; 4 = as 0 but fp8 codes widened to bf16 (the round-2 build: the A/B switch) */
+                                        matrix instruction (query as two e4m3 pieces); 1, 2, 3 = as 0 (1 and 2 chose 512-thread builds, since
+                                        retired); 4 = as 0 but fp8 codes widened to bf16 (the round-2 build: the A/B switch) */
     HVX_OPT_FLAT_NO_SMALLB = 8,      /* 1: batches of <= 128 queries do not take the one-pass streaming kernels; 2: batches of <= 32 queries stay on
                                         the register-fragment build (rows straight into MFMA operands) instead of the LDS-ring build */
     HVX_OPT_HNSW_PAIR = 9,           /* owner / gatherer kernel (an owner wavefront + 1 or 3 gatherer wavefronts per query): 0 = when the
                                         handle runs one query per SIMD (hvx_index_set_occupancy(1): one batch in flight), 1 = never,
                                         2 = always where it is built, 3 = always, with ONE gatherer even where three are built */
-    HVX_OPT_DELETE_SEQUENTIAL = 10,  /* 0: one fused launch per relinked row (round 6); 1: every source in the one-wavefront kernel; 2: two launches per row
-                                        (rows of at most 34 ids, degree limits <= 32) -- all three produce the reference's rows */
+    HVX_OPT_DELETE_SEQUENTIAL = 10,  /* 0: one fused launch per relinked row (round 6); 1: every source in the one-wavefront kernel; 2: as 0 (it chose
+                                        two launches per row, since retired) -- both produce the reference's rows */
     HVX_OPT_RESTRICTED_DIRECT = 11,  /* restricted exact scans of k <= 64: 0 = the one-launch reference-order kernel (csrc/hvx_restricted_exact.hip) where it is
                                         the cheaper one (b x candidates x dim <= 2^31), 1 = never, 2 = always */
     HVX_OPT_RESTRICTED_EXACT_MIB = 12, /* device plan of HVX_RESTRICTED_AUTO: candidate sets whose rows take at most this many MiB are scanned

@@ -1,4 +1,5 @@
 #!/bin/bash
+# HISTORY: drives the 512-thread tile build and its ablation switches, both retired (kept as the record of profiles/history/r02g_*).
 # usage (on the GPU box): scripts/ablate_tile.sh <tag> <bench_flat args...>
 # kernel time of the two-buffer 256 x 256 build with parts switched off (HVX_FLAT_TILE_ABLATE: 1 no operand copies, 2 no MFMAs,
 # 4 no epilogue) -> which phase bounds the tile.  Results of ablated runs are wrong by construction; only the timing is read.

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """A/B of the exact-scan tile kernel builds inside ONE process (tuning library: HVX_FLAT_TILE_BUILD is read per launch).
 For every build: ms per scan (device timer of the call), and whether the returned ids / score bits equal the default build's.
-usage: HVX_LIB_PATH=helix-db_amd/libhelix_vec_gfx950_tuning.so python scripts/tile_ab.py --dtype bf16 --builds 0,4,6"""
+usage: HVX_LIB_PATH=helix-db_amd/libhelix_vec_gfx950_tuning.so python scripts/tile_ab.py --dtype bf16 --builds 0,4,6
+HISTORY: the builds it compares besides 0 / 4 were retired (profiles/history/r04j_tile_builds_ab.txt is their record)."""
 import argparse, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "helix-db_amd"))

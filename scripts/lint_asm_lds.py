@@ -4,8 +4,8 @@
 The compiler believes an inline-asm output is valid as soon as the asm statement has executed, so nothing stops it from moving,
 copying (v_mov / v_accvgpr_write) or consuming such a register before the LDS has answered; the kernels state their own
 `s_waitcnt lgkmcnt(N)` instead.  This lint reports any instruction that touches a register a `ds_read` has requested but that no
-`s_waitcnt lgkmcnt` has covered yet.  (Found on hardware first: the fp8 instantiation of flat_tile4_kernel, at 256 VGPRs + 256
-AGPRs, copied fragment registers with v_mov right behind their ds_read and returned wrong candidates.)
+`s_waitcnt lgkmcnt` has covered yet.  (Found on hardware first: the fp8 instantiation of the since retired flat_tile4_kernel, at
+256 VGPRs + 256 AGPRs, copied fragment registers with v_mov right behind their ds_read and returned wrong candidates.)
 
 Method: the kernel's text is cut into basic blocks (labels, s_branch / s_cbranch_* / s_endpgm), a forward data-flow pass carries
 the set of registers with an outstanding request across the edges (union over predecessors, iterated to a fixed point), and

@@ -349,26 +349,28 @@ def test_host_traversal_equals_the_oracle_in_both_strategies(orc):
         hv.traverse_host(4, off[:5] * 0, np.zeros(0, np.uint64), None, [9], 1)                                # unknown seed
 
 
-def test_inline_asm_lds_reads_are_covered_by_a_wait(tmp_path):
+def test_inline_asm_lds_reads_of_both_tile_builds_are_covered_by_a_wait(tmp_path):
     """The large-tile exact-scan kernels read their MFMA fragments with inline-asm ds_read_b128 and state the lgkmcnt waits
     themselves; the compiler treats an asm output as valid at once and may copy / consume it before the LDS has answered
-    (seen on hardware: the fp8 instantiation of flat_tile4_kernel returned wrong candidates).  scripts/lint_asm_lds.py walks
-    the control-flow graph of the gfx950 assembly: no instruction may touch a requested register before a covering wait."""
+    (seen on hardware: the fp8 instantiation of the since retired flat_tile4_kernel returned wrong candidates).  scripts/lint_asm_lds.py
+    walks the control-flow graph of the gfx950 assembly: no instruction may touch a requested register before a covering wait -- in
+    both builds that remain (flat_tile2_kernel, bf16 and fp8 instantiations, and flat_tile2mx_kernel), release and tuning libraries."""
     import shutil
     import subprocess
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("no hipcc")
     src = os.path.join(ROOT, "helix-db_amd", "csrc", "hvx_flat_tile.hip")
-    # the release build carries flat_tile2_kernel only; the tuning build (-DHVX_TUNING) also the experimental flat_tile4_kernel
-    for flags, kernels, want in (([], ["flat_tile2_kernel"], 2), (["-DHVX_TUNING"], ["flat_tile2_kernel", "flat_tile4_kernel"], 6)):
-        asm = tmp_path / ("hvx_flat_tile%d.s" % want)
+    for tag, flags in (("release", []), ("tuning", ["-DHVX_TUNING"])):
+        asm = tmp_path / ("hvx_flat_tile_%s.s" % tag)
         out = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-S", "--cuda-device-only"]
                              + flags + ["-o", str(asm), src], capture_output=True, text=True)
         assert out.returncode == 0, out.stderr
-        lint = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "lint_asm_lds.py"), str(asm)] + kernels, capture_output=True, text=True)
+        lint = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "lint_asm_lds.py"), str(asm), "flat_tile2_kernel", "flat_tile2mx_kernel"],
+                              capture_output=True, text=True)
         assert lint.returncode == 0, lint.stdout + lint.stderr
-        assert lint.stdout.count(": 0 hazard(s)") == want, lint.stdout    # fp8 + bf16 instantiations of each kernel (tile4: with and without interleaved copies)
+        assert lint.stdout.count(": 0 hazard(s)") == 3, lint.stdout    # flat_tile2_kernel<0>, <1> and flat_tile2mx_kernel
+        assert lint.stdout.count("flat_tile2_kernel") == 2 and lint.stdout.count("flat_tile2mx_kernel") == 1, lint.stdout
 
 
 def test_asm_lint_flags_an_inline_asm_read_inside_a_matrix_write_back_window(tmp_path):
@@ -476,7 +478,7 @@ def test_release_library_reads_no_environment_and_carries_no_measurement_code():
 
 
 def test_tile_workgroup_mapping_covers_every_tile_once():
-    """tile_coords / launch_flat_tile256 (csrc/hvx_flat_tile.hip): workgroup id -> (row tile, query tile) through XCD-aware
+    """tile_coords / launch_flat_tile (csrc/hvx_flat_tile.hip): workgroup id -> (row tile, query tile) through XCD-aware
     super-tiles.  A tile that no workgroup computes is a stretch of rows that is never scanned -- and nothing downstream could
     notice -- so a python twin of the arithmetic sweeps ragged shapes: every (row tile, query tile) exactly once, the rest of
     the grid out of range, for the 64-workgroup (two per CU) and the 32-workgroup (one per CU) super-tiles."""

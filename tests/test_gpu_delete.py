@@ -56,15 +56,15 @@ def assert_same_graph(gix, oix, ids, deleted):
 @pytest.mark.parametrize("n,dim,metric,m,m0,efc,kern,relink", [(1600, 128, 1, 16, 32, 100, "avx_fma", "steps"), (1200, 256, 0, 16, 32, 80, "avx_fma", "steps"),
                                                                (1000, 72, 2, 8, 16, 60, "avx_fma", "steps"), (1200, 768, 1, 16, 32, 100, "avx_fma", "steps"),
                                                                (900, 88, 1, 8, 16, 60, "neon", "one_wavefront"),
-                                                               (1100, 128, 0, 16, 32, 80, "avx_fma", "two_launch_steps")])
+                                                               (1100, 128, 0, 16, 32, 80, "avx_fma", "steps")])
 def test_sequential_deletes_equal_the_oracles_row_for_row(orc, hv, n, dim, metric, m, m0, efc, kern, relink):
     """VectorIndex::delete one node at a time (mutation.rs:1606-1774): after three batches of deletes (scattered ids, the entry point
     twice, ids that are unknown, an id twice in one batch) every layer-0 row, every upper row, the entry point and the top layer of
     the live nodes equal the oracle's; deleted ids are gone from the HNSW searches (strict + the production default arm), the exact
     scan, restricted candidate sets and hvx_index_contains; the statistics count what happened; a fork adopts the owner's generation at its next launch
     (in-place rewrites cannot be hidden from it); rows appended AFTER the deletes link exactly as the oracle's do.  Every relink path of the device (one fused launch per
-    source with all its prunes' distance matrices evaluated up front; two launches per source; the one-wavefront kernel with the lazy
-    select_diverse) produces the same rows."""
+    source with all its prunes' distance matrices evaluated up front; the one-wavefront kernel with the lazy select_diverse) produces the
+    same rows."""
     ok, hk = {"avx_fma": (orc.K_AVX_FMA, hv.KERNEL_AVX_FMA), "neon": (orc.K_NEON, hv.KERNEL_NEON)}[kern]
     rng = np.random.default_rng(4200 + dim + metric + n)
     n_all = n + 120
@@ -80,8 +80,6 @@ def test_sequential_deletes_equal_the_oracles_row_for_row(orc, hv, n, dim, metri
     assert_same_graph(gix, oix, ids[:n], ())
     if relink == "one_wavefront":
         gix.set_option(hv.OPT_DELETE_SEQUENTIAL, 1)
-    elif relink == "two_launch_steps":   # the steps rows wider than 34 ids take (default: one fused launch per relinked row)
-        gix.set_option(hv.OPT_DELETE_SEQUENTIAL, 2)
     gix.set_simhash()
     lane = gix.fork()
     seq0 = gix.visible_seq()
@@ -312,12 +310,14 @@ def test_an_upsert_into_a_slot_refreshes_the_caches_of_the_matrix_core_scan(orc,
 
 
 @pytest.mark.parametrize("n,dim,metric", [(1400, 128, 1), (1000, 256, 0), (700, 768, 1)])
-def test_deletes_on_a_bf16_image_equal_the_oracle_on_the_rounded_rows(orc, hv, n, dim, metric):
+def test_deletes_on_a_bf16_image_equal_the_oracle_and_refuse_the_one_wavefront_kernel(orc, hv, n, dim, metric):
     """BASELINE config #4's storage (rows rounded to bf16 once at import, interleaved device layout): hvx_index_delete_batch relinks on
     the resident bf16 rows -- the ranking and every prune's distance matrix in f32 on the rounded values, in the reference's summation
     order -- so rows, entry point and top layer equal the oracle's deletes on the ROUNDED vectors after two batches (scattered ids and
     the entry point); the searches (strict arm + production default), the exact scan and a restricted scan equal the oracle's bit for
-    bit afterwards.  Paths that read f32 rows refuse a bf16 image loudly (one-wavefront relinks, two-launch steps)."""
+    bit afterwards.  The path that reads f32 rows refuses a bf16 image loudly (one-wavefront relinks, HVX_OPT_DELETE_SEQUENTIAL = 1) and
+    changes nothing; HVX_OPT_DELETE_SEQUENTIAL = 2 (it chose the retired two-launch steps, refused here too) now runs the fused steps:
+    the next delete equals the oracle's as well."""
     rng = np.random.default_rng(9100 + dim + metric)
     data = rng.standard_normal((n, dim)).astype(np.float32)
     rounded = fx.round_bf16(data)
@@ -368,12 +368,16 @@ def test_deletes_on_a_bf16_image_equal_the_oracle_on_the_rounded_rows(orc, hv, n
         assert rid[qi, :rcnt[qi]].tolist() == tid.tolist() and bits(rsc[qi, :rcnt[qi]]).tolist() == bits(tsc).tolist()
         assert not (set(gid[qi, :gcnt[qi]].tolist()) | set(fid[qi, :fcnt[qi]].tolist()) | set(rid[qi, :rcnt[qi]].tolist())) & dset
     live = [int(x) for x in ids if int(x) not in dset]
-    for opt in (1, 2):                                                         # the relink paths that read f32 rows
-        gix.set_option(hv.OPT_DELETE_SEQUENTIAL, opt)
-        with pytest.raises(hv.HelixDbError):
-            gix.delete_batch(np.asarray(live[:1], np.uint64))
-    gix.set_option(hv.OPT_DELETE_SEQUENTIAL, 0)
+    gix.set_option(hv.OPT_DELETE_SEQUENTIAL, 1)                                # the relink path that reads f32 rows
+    with pytest.raises(hv.HelixDbError):
+        gix.delete_batch(np.asarray(live[:1], np.uint64))
     assert gix.live_rows() == n - len(deleted)                                 # ... refused before anything changed
+    assert_same_graph(gix, oix, ids, deleted)
+    gix.set_option(hv.OPT_DELETE_SEQUENTIAL, 2)                                # an alias of the default: the fused steps
+    assert oix.delete(live[0])[0] == orc.OK
+    assert gix.delete_batch(np.asarray(live[:1], np.uint64))["deleted"] == 1
+    deleted.append(live[0])
+    assert gix.live_rows() == n - len(deleted) == oix.count
     assert_same_graph(gix, oix, ids, deleted)
     gix.close()
 

@@ -1373,16 +1373,16 @@ def test_exact_scan_through_the_256_tile_kernel(orc, hv, dtype_name, metric, dim
 
 @pytest.mark.parametrize("dtype_name,metric,dim,n,k,b", [TILE_CASES[0], TILE_CASES[2]])
 def test_exact_scan_through_the_512_thread_tile_build(orc, hv, dtype_name, metric, dim, n, k, b):
-    """HVX_OPT_FLAT_TILE_BUILD = 1: the one-workgroup-per-CU build (256 x 256 tiles, two 64-deep LDS buffers; in tuning builds
-    it carries the measurement switches) -- same answers as the default build and the oracle."""
+    """HVX_OPT_FLAT_TILE_BUILD = 1 chose the one-workgroup-per-CU build (256 x 256 tiles, two 64-deep LDS buffers), since retired: the
+    value stays accepted and runs the default build -- same answers as the 128 x 128 kernel and the oracle."""
     test_exact_scan_through_the_256_tile_kernel(orc, hv, dtype_name, metric, dim, n, k, b, tile_build=1)
 
 
 @pytest.mark.parametrize("dtype_name,metric,dim,n,k,b", TILE_CASES)
 def test_exact_scan_through_the_role_split_tile_build(orc, hv, dtype_name, metric, dim, n, k, b):
-    """HVX_OPT_FLAT_TILE_BUILD = 2 (round 4): 512 threads on a 256 x 256 tile with the two wavefronts of every SIMD in opposite roles
-    (one issues its MFMAs at priority while the other has its fragment reads and LDS-DMA copies in flight; raw barriers, counted
-    waits) -- bf16 / fp8 / f32-shadow rows, ragged tiles, a rejected query: the same answers as the 128 x 128 kernel and the oracle."""
+    """HVX_OPT_FLAT_TILE_BUILD = 2 chose the role-split build (round 4: 512 threads on a 256 x 256 tile, the two wavefronts of every SIMD
+    in opposite roles), since retired: the value stays accepted and runs the default build -- bf16 / fp8 / f32-shadow rows, ragged
+    tiles, a rejected query: the same answers as the 128 x 128 kernel and the oracle."""
     test_exact_scan_through_the_256_tile_kernel(orc, hv, dtype_name, metric, dim, n, k, b, tile_build=2)
 
 
@@ -1399,6 +1399,33 @@ def test_exact_scan_through_the_mx_fp8_tile_build(orc, hv, dtype_name, metric, d
 def test_exact_scan_through_the_bf16_widening_fp8_tile_build(orc, hv, dtype_name, metric, dim, n, k, b):
     """HVX_OPT_FLAT_TILE_BUILD = 4: fp8 codes widened to bf16 in registers (the default until round 4; the MX build's A/B partner)."""
     test_exact_scan_through_the_256_tile_kernel(orc, hv, dtype_name, metric, dim, n, k, b, tile_build=4)
+
+
+@pytest.mark.parametrize("dtype_name,metric,dim,n,k,b", [TILE_CASES[0], TILE_CASES[2]])
+def test_retired_tile_and_delete_options_stay_accepted_as_the_default(hv, dtype_name, metric, dim, n, k, b):
+    """HVX_OPT_FLAT_TILE_BUILD 1 and 2 chose the retired 512-thread tile builds, HVX_OPT_DELETE_SEQUENTIAL 2 the retired two-launch delete
+    steps; the values stay accepted (option ABI).  Tile builds 1 and 2 run the default build: the large-tile path, ids and score bits
+    equal to build 0's (fp8 rows: the MX build)."""
+    rng = np.random.default_rng(7100 + dim + n)
+    centers = rng.standard_normal((32, dim)).astype(np.float32)
+    data = (centers[rng.integers(0, 32, n)] + 0.5 * rng.standard_normal((n, dim))).astype(np.float32)
+    if dtype_name == "fp8":
+        data *= rng.uniform(0.2, 3.0, (n, 1)).astype(np.float32)
+    dt = {"bf16": hv.BF16, "fp8": hv.FP8_E4M3}[dtype_name]
+    q = (centers[rng.integers(0, 32, b)] + 0.5 * rng.standard_normal((b, dim))).astype(np.float32)
+    got = {}
+    for tb in (0, 1, 2):   # a fresh handle per build: after two scans whose one-pass attempt missed, a handle skips that attempt (and the tile)
+        gix = hv.ValidatedVectorReadIndex.managed(dim=dim, metric=metric, node_ids=np.arange(n, dtype=np.uint64), vectors=data, dtype=dt,
+                                                  l0_offsets=np.zeros(n + 1, np.uint64), l0_neighbors=np.zeros(0, np.uint64), max_batch=b)
+        gix.set_option(hv.OPT_FLAT_FIRST_CHUNK, 2048)
+        gix.set_option(hv.OPT_FLAT_NO_SMALLB, 1)                       # (batches of <= 128 queries would take the small-batch kernel)
+        gix.set_option(hv.OPT_FLAT_TILE_BUILD, tb)
+        gix.set_option(hv.OPT_DELETE_SEQUENTIAL, 2)                    # (accepted: an alias of 0)
+        gid, gsc, gcnt, _ = gix.flat_search_batch(q, k)
+        assert gix.last_scan_path() & hv.PATH_TILE_256, (tb, gix.last_scan_path())
+        got[tb] = (gid.tolist(), bits(gsc).tolist(), gcnt.tolist())
+        gix.close()
+    assert got[1] == got[0] and got[2] == got[0]
 
 
 def test_mx_scaled_mfma_operand_layout():
