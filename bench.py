@@ -3,22 +3,24 @@
 
 One "step" = one pass of the hot path over one batch of 1024 synthetic queries (config #2:
 1M x 768 f32, HNSW M=16/M0=32, ef_search=128, k=10) with index AND queries already resident in HBM.
-Contract (driver): `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line on rank 0 -- the LAST line of stdout, a
-compact record (< 4 KB, strict JSON: metric / value / config / roofline / cpu_baseline / parity + one-line summaries of the other
-legs).  Everything else every leg measured goes to `bench_full.json` next to this file (path in the line's `full_record`).
+Contract (driver): `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line on rank 0 -- the LAST line of stdout.  Such a
+plain run does only what the headline needs: corpus, graph, lanes, W + K steps, `--dump-outputs`, and a line of the contract keys
+(metric / value / unit / ms_per_step / higher_is_better / dtype ...) and the configuration.  `--full` adds every other leg below and
+prints a compact record instead (< 4 KB, strict JSON: + roofline / cpu_baseline / parity + one-line summaries of the other legs);
+everything else every leg measured goes to `bench_full.json` next to this file (path in the line's `full_record`).
 
 Steps are issued round-robin on `--lanes` execution lanes (hvx_index_fork: same index image, own stream + scratch), so
 that consecutive batches overlap on the device -- the way a serving host keeps the device fed: a batch that is still
 finishing its slowest queries no longer leaves SIMDs idle.  Nothing synchronises inside the timed region; `ms_per_step` is
-the host wall time of the K steps / K, `roofline.achieved` = algorithmic bytes per launch / (HIP-event span of the K
-search kernels / K).  The latency of ONE lone batch is reported next to it (`roofline.lone_batch`).
+the host wall time of the K steps / K.  With `--full`, `roofline.achieved` = algorithmic bytes per launch / (HIP-event span of
+the K search kernels / K), and the latency of ONE lone batch is reported next to it (`roofline.lone_batch`).
 
 N > 1 (launched by torch.distributed.run, one rank per GPU): the corpus is sharded by vector-id range, every rank
 searches the whole query batch on its shard, per-shard top-k are exchanged with ONE all-gather of a packed payload and
-merged on the device by Candidate order.  Two modes are measured in the same run: weak (`--rows` PER GPU, the corpus
-grows with N; the headline, ideal = constant QPS) and strong (`--rows` in total, 1/N per GPU; `strong_scaling`).
+merged on the device by Candidate order.  The headline is weak scaling (`--rows` PER GPU, the corpus grows with N; ideal =
+constant QPS); `--full` also measures strong scaling (`--rows` in total, 1/N per GPU; `strong_scaling`).
 
-The CPU oracle (oracle/) is used here ONLY as (a) the `cpu_baseline` leg and (b) a bit-exact checker of the GPU
+The CPU oracle (oracle/) is used here ONLY by `--full`, as (a) the `cpu_baseline` leg and (b) a bit-exact checker of the GPU
 results; the timed product path is the HIP library through its C ABI.
 """
 from __future__ import annotations
@@ -56,8 +58,8 @@ HEADLINE_KERNEL = "hnsw_wave_kernel<1u, 3, 24, false, false, false, true, 2, fal
 
 
 def measure_traffic_pass(args, timeout_s=150):
-    """roofline.traffic of THIS run: a child `rocprofv3 --pmc FETCH_SIZE TCC_EA0_RDREQ_sum --kernel-trace` pass of the headline leg of this
-    command (its own pass, counters + kernel trace only -- MI355X_MICROARCH.md, HBM section), FETCH_SIZE KiB x 1024 x 2 (gfx950 reports
+    """roofline.traffic of THIS run: a child `rocprofv3 --pmc FETCH_SIZE TCC_EA0_RDREQ_sum --kernel-trace` pass of a plain run (the headline leg
+    only) of this command (its own pass, counters + kernel trace only -- MI355X_MICROARCH.md, HBM section), FETCH_SIZE KiB x 1024 x 2 (gfx950 reports
     half of a wide coalesced read), mean over the headline kernel's 3 warm-up + 6 timed launches; cross-check TCC_EA0_RDREQ_sum x 128 B.
     Returns None (and the caller keeps the labelled static figure) when rocprofv3 is absent, the pass fails or times out."""
     import csv
@@ -68,12 +70,10 @@ def measure_traffic_pass(args, timeout_s=150):
     if os.environ.get("HVX_BENCH_CHILD") or not shutil.which("rocprofv3"):
         return None
     out_dir = tempfile.mkdtemp(prefix="hvx_pmc_", dir="/tmp")
-    skip = "production,production_lanes,insert,batcher,datasets,iso_recall,latent,config3,config4,config5,graph_equivalence,ef_sweep,vendor_gemm,peak,traffic"
     cmd = ["rocprofv3", "--pmc", "FETCH_SIZE", "TCC_EA0_RDREQ_sum", "--kernel-trace", "--output-format", "csv", "-d", out_dir, "-o", "pmc", "--",
-           sys.executable, os.path.abspath(__file__), "--steps", "6", "--warmup", "3", "--skip", skip, "--cpu-seconds", "0", "--no-verify",
+           sys.executable, os.path.abspath(__file__), "--steps", "6", "--warmup", "3",
            "--rows", str(args.rows), "--batch", str(args.batch), "--seed", str(args.seed), "--lanes", str(args.lanes), "--occupancy", str(args.occupancy),
-           "--m", str(args.m), "--builder", args.builder, "--build-batch", str(args.build_batch),
-           "--full-record", os.path.join(out_dir, "child_full.json")]
+           "--m", str(args.m), "--builder", args.builder, "--build-batch", str(args.build_batch)]
     env = dict(os.environ, HVX_BENCH_CHILD="1", TMPDIR="/tmp")
     t0 = time.time()
     try:
@@ -146,6 +146,10 @@ def parse():
     ap.add_argument("--traffic-file", default=os.path.join(ROOT, "profiles", "traffic_latest.json"))
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="after the headline's timed steps, write what its last step returned (ids, scores, counts, status) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg (recall, roofline with the lone batch, traffic and stream-read passes, ef sweep, "
+                         "production default, cpu_baseline + oracle parity, batcher, other corpora and configs, strong scaling) and write the "
+                         "full record; --skip, --scaling, --cpu-seconds, --no-verify, --deadline and --full-record apply to it")
     return ap.parse_args()
 
 
@@ -165,7 +169,7 @@ def build_graph(hv, synth, args, x, metric, id_lo, b, device, level_seed, keep_i
     """The benchmark graph.  'device' (default): hvx_index_build -- the reference's insert_hnsw for batches of nodes on the
     GPU (csrc/hvx_build.hip), M / M0 = 2M / ef_construction 200, levels from the reference's layer rule; 'bulk': the
     round-1 harness builder (pyhvx/synth.py: exact kNN + select_diverse).  Returns (graph dict with external ids, info,
-    the built f32 index or None)."""
+    the built f32 index or None); the graph dict is None when a plain run keeps the built index (it reads nothing back)."""
     n = x.shape[0]
     ids = np.arange(n, dtype=np.uint64) + np.uint64(id_lo)
     t0 = time.time()
@@ -186,15 +190,18 @@ def build_graph(hv, synth, args, x, metric, id_lo, b, device, level_seed, keep_i
                                                     search_max_batch=b)
         bix.sync()
         secs = time.time() - t0
-        g = bix.export_graph()
-        g["node_ids"] = ids
         info = {"builder": "hvx_index_build: insert_hnsw (mutation.rs:787-895) for batches of nodes on the device, M=%d M0=%d efC=200" % (args.m, 2 * args.m),
                 "seconds": round(secs, 2), "inserts_per_s": round(n / secs, 1), "batches": int(st["batches"]), "max_batch": args.build_batch}
-        # every graph the bench searches is audited where it was built (hvx_index_audit_graph: row invariants of neighbor_set.rs:1-9,
-        # symmetry on every layer -- mutation.rs:1498-1583,1890-1908 --, layer-0 reachability from the entry point)
-        t1 = time.time()
-        info["audit"] = graph_audit(bix, args.m)
-        info["audit"]["seconds"] = round(time.time() - t1, 3)
+        if keep_index and not args.full:  # the host copy of the graph serves --full's legs and checks, and the import of bf16 rows
+            return None, info, bix
+        g = bix.export_graph()
+        g["node_ids"] = ids
+        if args.full:
+            # every graph a --full run searches is audited where it was built (hvx_index_audit_graph: row invariants of neighbor_set.rs:1-9,
+            # symmetry on every layer -- mutation.rs:1498-1583,1890-1908 --, layer-0 reachability from the entry point)
+            t1 = time.time()
+            info["audit"] = graph_audit(bix, args.m)
+            info["audit"]["seconds"] = round(time.time() - t1, 3)
         if not keep_index:
             bix.close()
             bix = None
@@ -1499,7 +1506,7 @@ def main():
         t0 = time.time()
         ix = bix if bix is not None else import_index(hv, x, g, hv_metric, hv.BF16 if bf16 else hv.F32, b, local_rank)
         ix_truth = ix
-        if bf16:
+        if bf16:  # (a plain run makes it too: HIP assigns hardware queues in stream creation order, so the lanes get the queues of --full)
             ix_truth = hv.ValidatedVectorReadIndex.managed(
                 dim=dim, metric=hv_metric, node_ids=g["node_ids"], vectors=x, l0_offsets=np.zeros(n + 1, np.uint64),
                 l0_neighbors=np.zeros(0, np.uint64), device=local_rank, max_batch=b)
@@ -1545,6 +1552,10 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed, span = float(t[0].item()), float(t[1].item())
         qps = b * args.steps / elapsed * (world if replica else 1)
+        if not args.full:  # the headline figure is complete: recall, counters and the checks below are --full's
+            assert int(ls.bufs[0][3].abs().sum().item()) == 0, "a query was rejected"
+            return (dict(timed_runs=timed_runs, host_stall=stall, qps=qps, ms_per_step=elapsed * 1e3 / args.steps, n=n, n_total=n_total,
+                         exchange=exchange, nbq=nbq), dict(ix=ix, ix_truth=ix_truth, ls=ls))
         # recall@k against the exact scan (itself bit-exact vs the oracle's flat scan, tests/test_gpu_parity.py)
         f = out_buffers(b, k, dev)
         ix_truth.flat_search_batch_device(q, k, *f[:4])  # first use loads the scan's code objects: not timed
@@ -1574,8 +1585,40 @@ def main():
         state = dict(ix=ix, ix_truth=ix_truth, ls=ls, x=x, q=q, g=g, truth=f, id_lo=id_lo, qs=qs)
         return res, state
 
+    def headline(res, ls):
+        """the contract keys and the configuration of the headline measurement: a plain run's line, and the head of --full's record"""
+        n = res["n"]
+        return {
+            "metric": "QPS @ recall@10>=0.95, 1Mx768 fp32; achieved HBM GB/s vs roofline", "value": round(res["qps"], 1),
+            "unit": "queries/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(res["ms_per_step"], 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32" if not bf16 else "f32 arithmetic on bf16 rows", "data": "synthetic",
+            "config": {"workload": f"configs[1]: {n}x{dim} {args.dtype} per GPU, HNSW M={args.m}/M0={2 * args.m} ef_search={ef} k={k}, "
+                                   f"batch={b} queries, {'cosine' if cosine else 'squared-L2'}, strict-exhaustive beam (bit-exact vs reference CPU path), "
+                                   f"steps issued round-robin on {lanes} execution lanes",
+                       "dataset": args.dataset, "rows_per_gpu": n, "rows_total": res["n_total"], "dim": dim, "batch": b, "k": k,
+                       "ef_search": ef, "lanes": lanes, "distinct_query_batches": res["nbq"],
+                       "exchange": res["exchange"],
+                       "rccl_ranks": (world if (world > 1 and ls.groups) else None), "rccl_version": (hv.rccl_version() if world > 1 else None),
+                       "parallelism": ("1 GPU" if world == 1 else f"{world} replicas, one query batch each" if replica
+                                       else f"id-range shards x{world} + all-gather top-k merge")}}
+
     n_weak_total = args.rows if replica else args.rows * world
     res, S = shard_run(n_weak_total, "weak" if world > 1 else "1 GPU", dump=True)
+    if not args.full:
+        out = headline(res, S["ls"])
+        if res["timed_runs"] != 1:
+            out.update(timed_runs=res["timed_runs"], host_stall_in_first_run=res["host_stall"])
+        if rank == 0:
+            sys.stderr.flush()
+            print(json.dumps(_finite(out), allow_nan=False, separators=(",", ":")), flush=True)
+        S["ls"].close_forks()
+        S["ix"].close()
+        if S["ix_truth"] is not S["ix"]:
+            S["ix_truth"].close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
     ix, ls, q, g, x = S["ix"], S["ls"], S["q"], S["g"], S["x"]
     S_qs = S["qs"]
     headline_alive = True
@@ -1672,19 +1715,7 @@ def main():
                 "per_query_expansion_steps": {"p50": pct(qst[:, 0], 50), "p99": pct(qst[:, 0], 99), "max": int(qst[:, 0].max())}}
 
     out = {
-        "metric": "QPS @ recall@10>=0.95, 1Mx768 fp32; achieved HBM GB/s vs roofline", "value": round(res["qps"], 1),
-        "unit": "queries/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(res["ms_per_step"], 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32" if not bf16 else "f32 arithmetic on bf16 rows", "data": "synthetic",
-        "config": {"workload": f"configs[1]: {n}x{dim} {args.dtype} per GPU, HNSW M={args.m}/M0={2 * args.m} ef_search={ef} k={k}, "
-                               f"batch={b} queries, {'cosine' if cosine else 'squared-L2'}, strict-exhaustive beam (bit-exact vs reference CPU path), "
-                               f"steps issued round-robin on {lanes} execution lanes",
-                   "dataset": args.dataset, "rows_per_gpu": n, "rows_total": res["n_total"], "dim": dim, "batch": b, "k": k,
-                   "ef_search": ef, "lanes": lanes, "distinct_query_batches": res["nbq"],
-                   "exchange": res["exchange"],
-                   "rccl_ranks": (world if (world > 1 and ls.groups) else None), "rccl_version": (hv.rccl_version() if world > 1 else None),
-                   "parallelism": ("1 GPU" if world == 1 else f"{world} replicas, one query batch each" if replica
-                                   else f"id-range shards x{world} + all-gather top-k merge")},
+        **headline(res, ls),
         "recall_at_10": round(res["recall"], 4),
         "timed_runs": res["timed_runs"], "host_stall_in_first_run": res["host_stall"], "host_timing": res["host_timing"],
         "shard_searches_per_s": round(res["qps"] * (1 if replica else world), 1),

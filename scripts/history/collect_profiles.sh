@@ -12,7 +12,7 @@ out=gpurun_out/prof_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 EXTRA="--skip production,datasets,config3,config4,config5,graph_equivalence --cpu-seconds 0 --no-verify"
-BENCH="python bench.py --steps 60 --warmup 6"
+BENCH="python bench.py --full --steps 60 --warmup 6"
 if [ -z "$SKIP_FULL" ]; then $BENCH 2> $out/bench.log | tail -1 > $out/bench_line.json; fi
 rm -rf /tmp/prof_$tag
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$tag -o $tag -- $BENCH $EXTRA > /tmp/prof_$tag.log 2>&1
@@ -42,7 +42,7 @@ grep '^{' /tmp/prof_${tag}l.log | tail -1 > $out/bench_line_profiled_lone_batch.
 pmc() {
   name=$1; shift
   rm -rf /tmp/pmc_$name
-  rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d /tmp/pmc_$name -o $name -- python bench.py --steps 6 --warmup 3 $EXTRA > /tmp/pmc_$name.log 2>&1
+  rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d /tmp/pmc_$name -o $name -- python bench.py --full --steps 6 --warmup 3 $EXTRA > /tmp/pmc_$name.log 2>&1
   f=$(ls /tmp/pmc_$name/*counter_collection.csv | head -1)
   (head -1 "$f"; grep -E "hnsw_(wave|search)_kernel" "$f") > $out/pmc_$name.csv
 }

@@ -9,7 +9,7 @@ tag=$1
 out=gpurun_out/prof_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
-C3="python bench.py --skip production,datasets,config4,config5,graph_equivalence --cpu-seconds 0 --no-verify --steps 10 --warmup 2"
+C3="python bench.py --full --skip production,datasets,config4,config5,graph_equivalence --cpu-seconds 0 --no-verify --steps 10 --warmup 2"
 rm -rf /tmp/c3_$tag
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/c3_$tag -o c3 -- $C3 > /tmp/c3_$tag.log 2>&1 || true
 grep '^{' /tmp/c3_$tag.log | tail -1 > $out/c3_bench_line.json

@@ -992,3 +992,21 @@ def test_bench_dump_outputs_writes_the_last_timed_step(tmp_path, monkeypatch):
     ids = np.load(tmp_path / "b" / "ids.npy")
     assert np.array_equal(ids, 2000 + np.arange(b * k, dtype=np.float64).reshape(b, k)[rows.astype(np.int64)])   # step 2: lane 2
     assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= bench.DUMP_LIMIT
+
+
+def test_bench_other_legs_need_full():
+    """`bench.py --gpus 1 --steps K --warmup W` is a plain run (the headline's steps and line: tests/test_gpu_bench.py); every other leg
+    and the full record run only with --full."""
+    import importlib.util
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py"]
+        spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+        bench = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(bench)
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"]
+        assert bench.parse().full is False
+        sys.argv = ["bench.py", "--full"]
+        assert bench.parse().full is True
+    finally:
+        sys.argv = argv
