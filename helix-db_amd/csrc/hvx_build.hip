@@ -20,7 +20,10 @@
 // Every distance is the reference-order f32 distance of hvx_device.h (group_distance), so `dist(c,s) < dist(c,q)` decisions
 // are the CPU path's.  Served shapes: f32 rows of any dimension, L2 / cosine / Manhattan, every summation tree (the unrolled
 // search builds for L2 / cosine + AVX+FMA + dim in {128,...,1536} + ef_construction <= 352, the GENERIC build of the same kernel
-// otherwise; select / link kernels per metric and tree), m0 <= 32, ef_construction <= 800.
+// otherwise; select / link kernels per metric and tree), m0 <= 64 (m <= 32), ef_construction <= 800.  The kernels of THIS file hold one id
+// per lane and 64-bit masks: degree limits up to 32.  Limits up to 64 (the reference's scale fixture, M 32 / M0 64) run the kernels of
+// hvx_build_wide.hip -- two ids per lane, 128-bit masks, 128 search candidates per layer and node -- picked per index in insert_range;
+// their one-node steps are the one-wavefront kernels (f32 and bf16 rows); their batches hold half the fraction and do not overlap search and link.
 // Round 3: the batched link step runs one WORKGROUP per link with the prune evaluated from LDS (build_link_wg_kernel below) and
 // the search side two wavefronts per SIMD for batches > 1 024 nodes: 1M x 768 in 4.1 s (round 2: 10.0 s).
 #include <hip/hip_runtime.h>
@@ -32,6 +35,7 @@
 
 #include "hvx_host.h"
 #include "hvx_graph_dev.h"
+#include "hvx_build_dev.h"
 
 using namespace hvx;
 
@@ -43,54 +47,6 @@ using namespace hvx;
 
 namespace hvx {
 
-#ifdef HVX_TUNING
-#define HVX_DBG_ADD(a, i, v) do { if ((a).dbg) atomicAdd(&(a).dbg[i], (uint32_t)(v)); } while (0)
-#else
-#define HVX_DBG_ADD(a, i, v) do { } while (0)
-#endif
-
-constexpr uint32_t kCand = 64; // candidates kept per layer and node (2 * Mmax <= 64)
-
-struct BuildArgs {
-    DevIndex ix;
-    uint32_t *l0, *up;          // the same rows as ix.l0 / ix.up, writable
-    uint32_t *locks;            // [n] one lock per row owner (all its layers)
-    const uint32_t *nodes;      // [b] internal ids of the batch
-    uint32_t b, layers;         // layers = old max_layer + 1
-    const uint64_t *cand_ids;   // [layers][b][kCand] internal ids (search output)
-    const float *cand_sc;       // [layers][b][kCand]
-    const uint32_t *cand_cnt;   // [layers][b]
-    uint32_t *sel;              // [layers][b][32] selected neighbours in selection order
-    uint32_t *sel_cnt;          // [layers][b]
-    uint32_t m, m0;             // degree limits: upper layers / layer 0 (m0 = max(m0, 2m), mutation.rs:178-196)
-    uint32_t *err;              // [1] set when a row would overflow its stride (invariant violation)
-    uint32_t ldp, ncmax;        // build_link_wg_kernel: row stride of a column block in LDS (floats), candidate rows the LDS holds
-    uint32_t link_ck;           // 32-float chunks per column block
-    uint32_t *dbg;              // tuning builds (HVX_BUILD_DEBUG): [0] lock spins [1] prunes [2] reverse-edge removals [3] plain appends
-    float *gdm;                 // one-node steps: [layers][kSeqLayerDm] distance matrices (device-scope stores / loads)
-    uint32_t *tick;             // ... [2][layers] workgroups that have delivered (zero between launches)
-    uint32_t g0, gu;            // ... workgroups of layer 0 / of every upper layer
-};
-
-__device__ __forceinline__ void lock_row(uint32_t *locks, uint32_t node, int lane) {
-    if (lane == 0) {
-        while (__hip_atomic_exchange(&locks[node], 1u, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != 0u) __builtin_amdgcn_s_sleep(2);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    __syncthreads();
-}
-__device__ __forceinline__ void unlock_row(uint32_t *locks, uint32_t node, int lane) {
-    __syncthreads();
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    if (lane == 0) __hip_atomic_store(&locks[node], 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// row of `node` on `layer`, and its stride
-__device__ __forceinline__ uint32_t *row_ptr(const BuildArgs &a, uint32_t node, uint32_t layer, uint32_t &stride) {
-    if (layer == 0u) { stride = a.ix.s0; return a.l0 + (size_t)node * a.ix.s0; }
-    stride = a.ix.su;
-    return a.up + (size_t)(a.ix.up_base[node] + layer - 1u) * a.ix.su;
-}
 
 // ---- step 2: the new node's own neighbour lists ----
 template <uint32_t METRIC, bool FUSED> __global__ __launch_bounds__(64) void build_select_kernel(BuildArgs a) {
@@ -541,49 +497,6 @@ static size_t link_lds_bytes(uint32_t ldp, uint32_t ncmax) {
            2u * ((link_pairs_max(ncmax) + 15u) & ~(size_t)15u);
 }
 
-// the tail of a link runs on ONE wavefront of the workgroup (the others have left): wavefront-level ordering instead of s_barrier
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-// Row locks of build_link_wg_kernel.  Everything a lock protects (the neighbour rows) is read and written with agent-scope
-// atomics (ld_row / st_row: coherent across the XCDs' L2s by themselves), so taking and dropping a lock needs ORDER only, not
-// cache maintenance: no acquire / release at agent scope (on gfx950 that is an L2 invalidate / write-back of the whole XCD per
-// link, with hundreds of links in flight), but relaxed atomics and an explicit wait for this wavefront's outstanding stores.
-__device__ __forceinline__ void lock_row_w(uint32_t *locks, uint32_t node, int lane) {
-    if (lane == 0) {
-        while (__hip_atomic_exchange(&locks[node], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) __builtin_amdgcn_s_sleep(2);
-    }
-    __builtin_amdgcn_wave_barrier(); // the row is read after lane 0 has left the loop (one wavefront: program order)
-    asm volatile("" ::: "memory");
-}
-__device__ __forceinline__ void unlock_row_w(uint32_t *locks, uint32_t node, int lane) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // every row store of this wavefront has been performed
-    __builtin_amdgcn_wave_barrier();
-    if (lane == 0) __hip_atomic_store(&locks[node], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// canonical row (ascending id, sentinel padded) of ids_lds[0..ns), written with agent-scope stores by one wavefront
-__device__ __forceinline__ void store_canonical_w(uint32_t *row, uint32_t stride, const uint32_t *ids_lds, uint32_t ns, int lane) {
-    const uint32_t mine = (uint32_t)lane < ns ? ids_lds[lane] : kSentinel;
-    uint32_t rank = 0;
-    for (uint32_t s = 0; s < ns; ++s) rank += ids_lds[s] < mine ? 1u : 0u;
-    if ((uint32_t)lane >= ns && (uint32_t)lane < stride) st_row(row + lane, kSentinel);
-    if ((uint32_t)lane < ns) st_row(row + rank, mine);
-}
-__device__ __forceinline__ void remove_edge_w(const BuildArgs &a, uint32_t layer, uint32_t owner, uint32_t victim, int lane) {
-    lock_row_w(a.locks, owner, lane);
-    uint32_t stride;
-    uint32_t *row = row_ptr(a, owner, layer, stride);
-    const uint32_t v = (uint32_t)lane < stride ? ld_row(row + lane) : kSentinel;
-    const bool keep = v != kSentinel && v != victim;
-    const unsigned long long km = __ballot(keep);
-    const uint32_t pos = (uint32_t)__builtin_popcountll(km & ((1ull << lane) - 1ull));
-    const uint32_t nk = (uint32_t)__builtin_popcountll(km);
-    if (keep) st_row(row + pos, v);   // every lane holds its id in a register: the order of the stores does not matter
-    if ((uint32_t)lane >= nk && (uint32_t)lane < stride) st_row(row + lane, kSentinel);
-    unlock_row_w(a.locks, owner, lane);
-}
 
 template <uint32_t METRIC, bool FUSED> __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void build_link_wg_kernel(BuildArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -904,7 +817,13 @@ static int insert_range(hvx_index *ix, uint64_t first, uint64_t count, const uin
         ix->ins_locks_rows = 0;
         return code;
     };
-    const size_t sz_cids = (size_t)layers_max * bmax * kCand, sz_cnt = (size_t)layers_max * bmax, sz_sel = (size_t)layers_max * bmax * 32;
+    if (std::max(m0, m) > 64u) return fail(HVX_ERR_UNSUPPORTED, "device build serves m0 <= 64 (m <= 32)");
+    if (std::max(m0, m) > 32u && (ix->dev.s0 > 64u || ix->dev.su > 64u || ix->dev.s0 < m0 || ix->dev.su < m))
+        return fail(HVX_ERR_UNSUPPORTED, "device build with m0 > 32 serves neighbour rows of m0 .. 64 ids");
+    // degree limits above 32: twice the candidates and selected neighbours per layer and node, and the kernels of hvx_build_wide.hip
+    const bool wide = std::max(m0, m) > 32u;
+    const uint32_t kc = wide ? kCandWide : kCand, selw = wide ? kSelWide : 32u;
+    const size_t sz_cids = (size_t)layers_max * bmax * kc, sz_cnt = (size_t)layers_max * bmax, sz_sel = (size_t)layers_max * bmax * selw;
     int rc;
     {
         auto up = [](size_t b) { return (b + 255u) & ~(size_t)255u; };
@@ -966,7 +885,9 @@ static int insert_range(hvx_index *ix, uint64_t first, uint64_t count, const uin
     const bool bf16 = d.dtype == HVX_BF16;
     if (bf16 && (!build_q || stride != 1u)) return sbail2(fail(HVX_ERR_INVARIANT, "bf16 rows are linked from their rounded f32 vectors"));
     const BuildKernels kern = pick_build_kernels(d.metric, fused, bf16);
-    const bool link_wg = params->link_mode != 1u && kern.link_wg && !kernel_w4(d.fkernel) /* 32-lane tree only */ && ncmax <= 33u && nk_rows > 0 && d.dim_main == d.dim && d.ld == d.dim &&
+    const WideLinkGeom wgeo = wide ? wide_link_geom(d, m, m0) : WideLinkGeom{};
+    const bool link_wg_wide = wide && params->link_mode != 1u && wgeo.ok;
+    const bool link_wg = !wide && params->link_mode != 1u && kern.link_wg && !kernel_w4(d.fkernel) /* 32-lane tree only */ && ncmax <= 33u && nk_rows > 0 && d.dim_main == d.dim && d.ld == d.dim &&
                          (size_t)(ncmax + 1u) * link_ck * 8u <= 9u * 256u;
     uint64_t done = first, batches = 0, singles = 0;
     if (!d.has_entry) { // the first node of an index: the entry point with empty rows on its layers (mutation.rs:706-739)
@@ -976,7 +897,10 @@ static int insert_range(hvx_index *ix, uint64_t first, uint64_t count, const uin
         done = first + 1;
         singles = 1;
     }
-    const uint32_t divisor = params->batch_divisor ? params->batch_divisor : 32u;
+    // (degree limits above 32: half the batch fraction -- a batch holds UP TO inserted / divisor nodes.  Nodes of a batch do not see each
+    // other, and at M 32 / M0 64 that costs more than the 0.01 of recall batching is granted: 8 000 x 128 Gaussian rows, divisor 16, ef 32:
+    // 0.8213 - 0.8240 against the sequential graph's 0.8326; with half the fraction 0.829)
+    const uint32_t divisor = (params->batch_divisor ? params->batch_divisor : 32u) * (wide ? 2u : 1u);
     bool prev_serial = true; // the previous batch must be complete before the next search starts
     // the iota / lock / err initialisation above ran on `s`: the link stream starts behind it
     if (hipEventRecord(ev_search[0], s) != hipSuccess || hipStreamWaitEvent(s2, ev_search[0], 0) != hipSuccess)
@@ -993,7 +917,9 @@ static int insert_range(hvx_index *ix, uint64_t first, uint64_t count, const uin
             while (bsz < want && !((levels ? levels[row_at(done + bsz)] : 0) > d.max_layer)) ++bsz;
         }
         const uint32_t pb = (uint32_t)(batches & 1u); // buffer set of this batch
-        const bool serial = promotes || bsz == 1u || params->sequential != 0u || params->link_mode == 1u;
+        // (degree limits above 32 do not overlap either: at M 32 / M0 64 a batch that sees neither its own nodes nor the batch before it
+        // costs 0.002 of recall@10 at ef 32 on 8 000 Gaussian rows -- 0.8216 against 0.8235 --, a fifth of the margin batching is granted)
+        const bool serial = promotes || bsz == 1u || params->sequential != 0u || params->link_mode == 1u || wide;
         // the buffers of set pb were last read by the link step of batch - 2; and a serial batch (or the batch behind one) starts
         // only when everything before it is in the graph
         if (link_pending[pb] && hipStreamWaitEvent(s, ev_link[pb], 0) != hipSuccess) return sbail2(fail(HVX_ERR_DEVICE, "stream ordering failed"));
@@ -1007,7 +933,7 @@ static int insert_range(hvx_index *ix, uint64_t first, uint64_t count, const uin
         a.ix = d;
         a.bitmap = ix->d_bitmap;
         a.words_per_query = ix->words_per_query;
-        a.k = kCand;
+        a.k = kc; // the first 2 * Mmax entries of W (mutation.rs:1072-1097)
         a.ef = ef0;
         a.build_ef_upper = efu;
         a.out_ids = b_cids;
@@ -1038,11 +964,30 @@ static int insert_range(hvx_index *ix, uint64_t first, uint64_t count, const uin
         ba.m0 = m0;
         ba.err = d_err;
         ba.dbg = d_dbg;
+        ba.kc = kc;
+        ba.selw = selw;
         // one node: its select and its links as two many-workgroup steps with every prune's distance matrix evaluated up front
-        const bool seq_step = bsz == 1u && (params->link_mode != 1u || bf16) && d.s0 + 1u <= kSeqRow && d.su + 1u <= kSeqRow;
-        if (bf16 && !seq_step) return sbail2(fail(HVX_ERR_UNSUPPORTED, "a bf16 image links rows of at most %u ids", kSeqRow - 1u));
+        const bool seq_step = !wide && bsz == 1u && (params->link_mode != 1u || bf16) && d.s0 + 1u <= kSeqRow && d.su + 1u <= kSeqRow;
+        if (bf16 && !seq_step && !wide) return sbail2(fail(HVX_ERR_UNSUPPORTED, "a bf16 image links rows of at most %u ids", kSeqRow - 1u));
         hipError_t e;
-        if (seq_step) {
+        if (wide) { // two ids per lane: the one-wavefront kernels for one node (f32 and bf16 rows), one workgroup per link for a batch
+            e = launch_build_select_wide(ba, fused, bf16, dim3(bsz, layers), s2);
+            if (e == hipSuccess) {
+                // The workgroup kernel reads 2 145 pairs x dim out of LDS per link: LDS-bandwidth bound, ~48 us per link at dim 768 with one
+                // workgroup per CU.  Once a batch has enough nodes for the one-wavefront kernel's dependent gathers to overlap across nodes
+                // (>= 1 024: four wavefronts per CU) that kernel is the faster link step -- 1M x 768, batches of 2 048: 13.9 s against 15.9 s --,
+                // below that the workgroup kernel is (8 000 x 128, batches <= 250: 0.22 s against 0.99 s).
+                constexpr uint32_t kWideWgMaxBatch = 1024;
+                if (bsz > 1u && bsz < kWideWgMaxBatch && link_wg_wide) {
+                    ba.ldp = wgeo.ldp;
+                    ba.ncmax = wgeo.ncmax;
+                    ba.link_ck = wgeo.link_ck;
+                    e = launch_build_link_wide_wg(ba, fused, layers, wgeo.lds, s2);
+                } else {
+                    e = launch_build_link_wide(ba, fused, bf16, bsz, s2);
+                }
+            }
+        } else if (seq_step) {
             ba.gdm = d_gdm;
             ba.tick = d_tick;
             ba.g0 = 63u; ba.gu = 16u; // 32 row groups per workgroup: 2 016 pairs among 64 candidates on layer 0, 496 among 32 above
@@ -1053,7 +998,7 @@ static int insert_range(hvx_index *ix, uint64_t first, uint64_t count, const uin
         } else {
             e = launch_build(kern.select, dim3(bsz, layers), ba, s2);
         }
-        if (e == hipSuccess && !seq_step) {
+        if (e == hipSuccess && !seq_step && !wide) {
             if (bsz > 1u && link_wg) { // batched mode: one workgroup per link, prunes evaluated from LDS
                 ba.ldp = ldp;
                 ba.ncmax = ncmax;
@@ -1107,7 +1052,7 @@ extern "C" int hvx_index_build(const hvx_index_desc *desc, const uint64_t *node_
     const uint32_t m0 = std::max(desc->m0 ? desc->m0 : 2u * m, 2u * m); // MutationDegreeLimits (mutation.rs:178-196)
     const uint32_t efc = params->ef_construction ? params->ef_construction : 200u;
     if (desc->dtype != HVX_F32) return fail(HVX_ERR_UNSUPPORTED, "the device build reads f32 rows (import the built graph with a reduced-precision dtype afterwards)");
-    if (m0 > 32u || m > 32u) return fail(HVX_ERR_UNSUPPORTED, "device build serves m0 <= 32");
+    if (m0 > 64u || m > 32u) return fail(HVX_ERR_UNSUPPORTED, "device build serves m0 <= 64 (m <= 32)");
     if (std::max(efc, m0) + 32u > 832u) return fail(HVX_ERR_UNSUPPORTED, "device build serves ef_construction <= 800");
     const uint32_t ef0 = std::max(efc, m0);
 
@@ -1184,7 +1129,9 @@ extern "C" int hvx_index_insert_batch(hvx_index *ix, const uint64_t *node_ids, c
     const uint32_t m = ix->desc.m ? ix->desc.m : 16u;
     const uint32_t m0 = std::max(ix->desc.m0 ? ix->desc.m0 : 2u * m, 2u * m);
     const uint32_t efc = params->ef_construction ? params->ef_construction : 200u;
-    if (m0 > 32u || m > 32u || d.s0 < m0 || d.su < m) return fail(HVX_ERR_UNSUPPORTED, "the image's neighbour rows are narrower than the degree limits (build it with hvx_index_build)");
+    if (m0 > 64u || m > 32u) return fail(HVX_ERR_UNSUPPORTED, "device inserts serve m0 <= 64 (m <= 32)");
+    if (d.s0 < m0 || d.su < m) return fail(HVX_ERR_UNSUPPORTED, "the image's neighbour rows are narrower than the degree limits (build it with hvx_index_build)");
+    if (m0 > 32u && (d.s0 > 64u || d.su > 64u)) return fail(HVX_ERR_UNSUPPORTED, "device inserts with m0 > 32 serve neighbour rows of <= 64 ids");
     if (std::max(efc, m0) + 32u > 832u) return fail(HVX_ERR_UNSUPPORTED, "device build serves ef_construction <= 800");
     const uint64_t n0 = d.n;
     if (n0 + count > ix->cap_rows)
@@ -1301,6 +1248,12 @@ extern "C" int hvx_index_upsert_batch(hvx_index *ix, const uint64_t *node_ids, c
     const uint32_t dim = ix->dev.dim, ld = ix->dev.ld;
     if (ix->dev.dtype != HVX_F32 && ix->dev.dtype != HVX_BF16) return fail(HVX_ERR_UNSUPPORTED, "rows are written into f32 and bf16 images");
     const bool bf16 = ix->dev.dtype == HVX_BF16; // (round 6: an id the image holds gets its new vector in its slot; bf16 images have no spare rows to append to)
+    { // the insert half's degree limits, before the delete half changes anything
+        const uint32_t m = ix->desc.m ? ix->desc.m : 16u;
+        const uint32_t m0 = std::max(ix->desc.m0 ? ix->desc.m0 : 2u * m, 2u * m);
+        if (m0 > 64u || m > 32u) return fail(HVX_ERR_UNSUPPORTED, "device upserts serve m0 <= 64 (m <= 32)");
+        if (m0 > 32u && (ix->dev.s0 > 64u || ix->dev.su > 64u)) return fail(HVX_ERR_UNSUPPORTED, "device upserts with m0 > 32 serve neighbour rows of <= 64 ids");
+    }
     // ---- every vector is validated before anything changes (an invalid one fails the call: mutation.rs:660-690) ----
     float *d_tmp = nullptr, *d_tmph = nullptr;
     uint32_t *d_st = nullptr;
@@ -1407,15 +1360,20 @@ extern "C" int hvx_index_link_rows(hvx_index *ix, const uint64_t *from_ids, cons
     const uint32_t nk_rows = d.dim_main >> 5;
     const uint32_t link_ck = std::min<uint32_t>(8u, (nk_rows + 1u) & ~1u);
     const uint32_t ldp = link_ck * 32u + 32u;
-    if (d.dtype != HVX_F32 || !kern.link_wg || kernel_w4(d.fkernel) || ncmax > 33u || nk_rows == 0 || d.dim_main != d.dim || d.ld != d.dim || d.s0 < m0 ||
-        (size_t)(ncmax + 1u) * link_ck * 8u > 9u * 256u)
-        return fail(HVX_ERR_UNSUPPORTED, "the link workgroups serve f32 rows, L2 / cosine, dim %% 32 == 0, m0 <= 32 (row stride >= m0)");
-    std::vector<uint32_t> h_nodes(n_links), h_sel((size_t)n_links * 32u, kSentinel), h_cnt(n_links, 1u);
+    const bool wide = std::max(m0, m) > 32u;
+    const WideLinkGeom wgeo = wide ? wide_link_geom(d, m, m0) : WideLinkGeom{};
+    const uint32_t selw = wide ? kSelWide : 32u;
+    if (std::max(m0, m) > 64u || (wide && (!wgeo.ok || d.s0 < m0)))
+        return fail(HVX_ERR_UNSUPPORTED, "the link workgroups serve f32 rows, L2 / cosine, dim %% 32 == 0, m0 <= 64 (row stride >= m0, <= 64)");
+    if (!wide && (d.dtype != HVX_F32 || !kern.link_wg || kernel_w4(d.fkernel) || ncmax > 33u || nk_rows == 0 || d.dim_main != d.dim || d.ld != d.dim || d.s0 < m0 ||
+        (size_t)(ncmax + 1u) * link_ck * 8u > 9u * 256u))
+        return fail(HVX_ERR_UNSUPPORTED, "the link workgroups serve f32 rows, L2 / cosine, dim %% 32 == 0, m0 <= 64 (row stride >= m0, <= 64)");
+    std::vector<uint32_t> h_nodes(n_links), h_sel((size_t)n_links * selw, kSentinel), h_cnt(n_links, 1u);
     for (uint32_t i = 0; i < n_links; ++i) {
         const uint32_t f = ix->find(from_ids[i]), t = ix->find(to_ids[i]);
         if (f == kSentinel || t == kSentinel || f == t) return fail(HVX_ERR_INVARIANT, "link %u: unknown id or a self link", i);
         h_nodes[i] = f;
-        h_sel[(size_t)i * 32u] = t;
+        h_sel[(size_t)i * selw] = t;
     }
     hipStream_t s = ix->stream;
     uint32_t *d_nodes = nullptr, *d_sel = nullptr, *d_cnt = nullptr, *d_locks = nullptr, *d_err = nullptr;
@@ -1424,7 +1382,7 @@ extern "C" int hvx_index_link_rows(hvx_index *ix, const uint64_t *from_ids, cons
             if (p) (void)hipFree(p);
     };
     auto bail = [&](int rc) { (void)hipStreamSynchronize(s); release(); return rc; };
-    if (hipMalloc((void **)&d_nodes, (size_t)n_links * 4) != hipSuccess || hipMalloc((void **)&d_sel, (size_t)n_links * 32 * 4) != hipSuccess ||
+    if (hipMalloc((void **)&d_nodes, (size_t)n_links * 4) != hipSuccess || hipMalloc((void **)&d_sel, (size_t)n_links * selw * 4) != hipSuccess ||
         hipMalloc((void **)&d_cnt, (size_t)n_links * 4) != hipSuccess || hipMalloc((void **)&d_locks, (size_t)d.n * 4) != hipSuccess ||
         hipMalloc((void **)&d_err, 4) != hipSuccess)
         return bail(fail(HVX_ERR_DEVICE, "hipMalloc of the link scratch failed"));
@@ -1444,22 +1402,24 @@ extern "C" int hvx_index_link_rows(hvx_index *ix, const uint64_t *from_ids, cons
     ba.m = m;
     ba.m0 = m0;
     ba.err = d_err;
-    ba.ldp = ldp;
-    ba.ncmax = ncmax;
-    ba.link_ck = link_ck;
-    const size_t lds = link_lds_bytes(ldp, ncmax);
+    ba.ldp = wide ? wgeo.ldp : ldp;
+    ba.ncmax = wide ? wgeo.ncmax : ncmax;
+    ba.link_ck = wide ? wgeo.link_ck : link_ck;
+    ba.selw = selw;
+    const size_t lds = wide ? wgeo.lds : link_lds_bytes(ldp, ncmax);
+    auto launch = [&]() { return wide ? launch_build_link_wide_wg(ba, fused, 1, lds, s) : launch_link_wg(kern.link_wg, ba, 1, lds, s); };
     hipError_t e = hipSuccess;
     if (concurrent) {
         ba.nodes = d_nodes;
         ba.b = n_links;
-        e = launch_link_wg(kern.link_wg, ba, 1, lds, s);
+        e = launch();
     } else {
         for (uint32_t i = 0; i < n_links && e == hipSuccess; ++i) { // one launch per link: launches on a stream run in order
             ba.nodes = d_nodes + i;
-            ba.sel = d_sel + (size_t)i * 32u;
+            ba.sel = d_sel + (size_t)i * selw;
             ba.sel_cnt = d_cnt + i;
             ba.b = 1;
-            e = launch_link_wg(kern.link_wg, ba, 1, lds, s);
+            e = launch();
         }
     }
     if (e != hipSuccess) return bail(fail(HVX_ERR_DEVICE, "link launch failed: %s", hipGetErrorString(e)));

@@ -588,7 +588,8 @@ class ValidatedVectorReadIndex:
               batch_divisor=32, sequential=False, device=-1, search_max_batch=None, float_kernel=KERNEL_AVX_FMA, link_mode=0, scatter=False,
               reserve_rows=0, reserve_upper_rows=None):
         """GPU-assisted HNSW build (hvx_index_build): the reference's insert_hnsw for batches of nodes on the device.
-        Returns (index, stats dict).  `vectors` may be a host array or a torch tensor resident on the device."""
+        Returns (index, stats dict).  `vectors` may be a host array or a torch tensor resident on the device.
+        Degree limits m0 <= 64 (m <= 32: the reference's scale configuration M 32 / M0 64 included); above: ERR_UNSUPPORTED."""
         ids = np.ascontiguousarray(node_ids, dtype=np.uint64)
         dev_rows = hasattr(vectors, "data_ptr")
         if dev_rows:
@@ -610,7 +611,8 @@ class ValidatedVectorReadIndex:
 
     def insert_batch(self, node_ids, vectors, levels=None, *, ef_construction=200, max_batch=2048, batch_divisor=32, sequential=False, link_mode=0):
         """hvx_index_insert_batch: append rows to a growable image (build(..., reserve_rows=...)) and link them into the graph; the new
-        generation is visible on this handle when the call returns (forks: refresh()).  Returns the build-stats dict of the batch."""
+        generation is visible on this handle when the call returns (forks: refresh()).  Returns the build-stats dict of the batch.
+        f32 and bf16 images with degree limits m0 <= 64 (m <= 32); above: ERR_UNSUPPORTED with nothing changed."""
         ids = np.ascontiguousarray(node_ids, dtype=np.uint64)
         dev_rows = hasattr(vectors, "data_ptr")
         if dev_rows:
@@ -629,7 +631,8 @@ class ValidatedVectorReadIndex:
 
     def upsert_batch(self, node_ids, vectors, levels=None, *, ef_construction=200):
         """hvx_index_upsert_batch: VectorInsertContract::Upsert -- a live id is deleted first, then the vector is linked in under the same
-        id (its own row slot, or appended when the id is above the image's); sequential semantics"""
+        id (its own row slot, or appended when the id is above the image's); sequential semantics.  f32 and bf16 images with degree
+        limits m0 <= 64 (m <= 32); above: ERR_UNSUPPORTED before the delete half runs."""
         ids = np.ascontiguousarray(node_ids, dtype=np.uint64).reshape(-1)
         vec = np.ascontiguousarray(vectors, dtype=np.float32).reshape(ids.size, self.dim)
         lv = None if levels is None else np.ascontiguousarray(levels, dtype=np.uint16).reshape(-1)
@@ -708,7 +711,8 @@ class ValidatedVectorReadIndex:
                 "entry_point": int(ep.value) if he.value else None, "max_layer": int(ml.value)}
 
     def link_rows(self, from_ids, to_ids, concurrent=False):
-        """add_bidirectional_link(from -> to) on layer 0 through the batched build's link kernel (hvx_index_link_rows)."""
+        """add_bidirectional_link(from -> to) on layer 0 through the batched build's link kernel (hvx_index_link_rows): the 256-thread
+        workgroup kernel for m0 <= 32, the 1 024-thread one for m0 <= 64."""
         f = np.ascontiguousarray(from_ids, dtype=np.uint64)
         t = np.ascontiguousarray(to_ids, dtype=np.uint64)
         assert f.size == t.size

@@ -660,12 +660,15 @@ int hvx_hydrator_finish_reserve(const hvx_hydrator *, const hvx_index_desc *tmpl
  * ordinary searchable hvx_index; hvx_index_export_graph hands the rows back for the host to persist (values/vectors.rs).
  * Served shapes: f32 rows of any dimension, cosine / Euclidean / Manhattan, every summation tree of the reference's float kernels
  * (the unrolled kernels for cosine / Euclidean + AVX+FMA + dim in {128,256,512,768,1024,1536} + ef_construction <= 352, the GENERIC
- * build otherwise), m0 <= 32, ef_construction <= 800; desc->max_batch bounds the batch size.
+ * build otherwise), m0 <= 64 (hence m <= 32: m0 = max(m0, 2 m); the reference's scale fixture runs M 32 / M0 64), ef_construction <= 800;
+ * desc->max_batch bounds the batch size.  Degree limits above 32 take the kernels of csrc/hvx_build_wide.hip (two ids per lane, 128-bit
+ * masks): same rows as the reference's insertion in sequential mode, same invariants in batches.  Larger limits: HVX_ERR_UNSUPPORTED
+ * before anything is allocated.
  */
 typedef struct hvx_build_params {
     uint32_t ef_construction; /* 0 => 200 (mod.rs:702-708) */
     uint32_t max_batch;       /* 0 => 2048 */
-    uint32_t batch_divisor;   /* 0 => 32: batch <= nodes already inserted / divisor */
+    uint32_t batch_divisor;   /* 0 => 32: batch <= nodes already inserted / divisor (degree limits above 32: / (2 * divisor)) */
     uint32_t sequential;      /* 1 => one node per batch: the reference's insertion order exactly */
     uint32_t link_mode;       /* batched link step: 0 => one workgroup per link with the prune evaluated from LDS whenever the rows fit
                                  (Mmax + 2 rows of ld floats <= 160 KB), 1 => one wavefront per node (links one after the other).
@@ -689,7 +692,8 @@ int hvx_index_build(const hvx_index_desc *desc, const uint64_t *node_ids, const 
  * Incremental insert into a LIVE image (VectorIndex::insert -> insert_hnsw, mutation.rs:642-895): `count` new nodes -- ids ascending
  * and above every id of the image, f32 vectors (host or device memory), levels as hvx_index_build takes them -- are appended to
  * the spare capacity of an image built with hvx_build_params.reserve_rows or hydrated with hvx_index_import_reserve
- * (HVX_ERR_CANDIDATE_LIMIT when they do not fit; bf16 images: the vectors are rounded first and linked one node at a time),
+ * (HVX_ERR_CANDIDATE_LIMIT when they do not fit; bf16 images: the vectors are rounded first and linked one node at a time), degree
+ * limits m0 <= 64 / m <= 32 on rows of at most 64 ids as hvx_index_build serves them (above: HVX_ERR_UNSUPPORTED, nothing changed),
  * validated like imported rows (an invalid vector fails the call before anything changes), given headers and -- when SimHash
  * rows are attached -- SimHash rows, and linked into the graph by the loop hvx_index_build runs: params->sequential = 1 is the
  * reference's insertion row for row (tests/test_gpu_build.py), the batched mode trades that for throughput exactly as the build
@@ -735,7 +739,8 @@ int hvx_index_delete_batch(hvx_index *, const uint64_t *node_ids /*[count]*/, ui
  * vector is validated before anything changes.  HVX_ERR_UNSUPPORTED for an id that lies between the image's ids without a slot.
  * Rows equal the oracle's delete + insert of the same ids (tests/test_gpu_delete.py).
  * bf16 images (round 6): the new vector is rounded to bf16, validated and linked over the bf16 rows (== the oracle on the rounded vectors);
- * appended ids need spare rows (hvx_index_import_reserve).  fp8 images are read-only.
+ * appended ids need spare rows (hvx_index_import_reserve).  fp8 images are read-only.  Degree limits as hvx_index_insert_batch
+ * (m0 <= 64, m <= 32; f32 and bf16 images alike), checked before the delete half runs.
  */
 int hvx_index_upsert_batch(hvx_index *, const uint64_t *node_ids /*[count]*/, const float *vectors /*[count][dim] host or device*/,
                            const uint16_t *levels /*[count] or NULL*/, uint32_t count, const hvx_build_params *params /*nullable*/,
@@ -750,10 +755,10 @@ uint64_t hvx_index_row_capacity(const hvx_index *); /* rows the image can hold *
  * add_bidirectional_link(from -> to) on layer 0 of an index image (mutation.rs:1498-1583): `from` is appended to the row of
  * `to` under the row's lock; a row beyond Mmax is pruned (rank by distance to the owner, select_diverse + backfill,
  * mod.rs:809-856), and every neighbour the prune drops loses its reverse edge (mutation.rs:1890-1908).  It runs the kernel the
- * BATCHED build links with (one 256-thread workgroup per link, the prune evaluated eagerly from LDS): the links are applied one
+ * BATCHED build links with (one workgroup per link -- 256 threads for m0 <= 32, 1 024 for m0 <= 64 --, the prune evaluated eagerly from LDS): the links are applied one
  * launch after the other in list order (concurrent = 0: a defined order, what the parity tests compare with the oracle's
  * select_diverse) or all in ONE launch (concurrent = 1: the batched build's situation -- rows change under their locks in an
- * undefined order).  Served shapes = the workgroup kernel's: f32 rows, L2 / cosine, dim % 32 == 0, m0 <= 32.  The index must
+ * undefined order).  Served shapes = the workgroup kernel's: f32 rows, L2 / cosine, dim % 32 == 0, m0 <= 64 (rows of at most 64 ids).  The index must
  * not be searched concurrently.
  */
 int hvx_index_link_rows(hvx_index *, const uint64_t *from_ids, const uint64_t *to_ids, uint32_t n_links, uint32_t concurrent);
