@@ -458,14 +458,17 @@ int hvx::import_index(const hvx_index_desc *desc, const uint64_t *node_ids, cons
         hipError_t e = hipSuccess;
         std::vector<float> h_n2(n);
         if (n) {
-            e = launch_f32_row_norm2(staging, (uint32_t)n, d.ld, d.dim, ix->m_rowterm, ix->stream);
+            // the exact scan's per-row term: |x|^2 for L2; cosine divides by the norm of the CODES (hvx_flat_mfma.hip, fp8_code_norm_kernel)
+            if (d.metric == kCosine) e = launch_fp8_code_norm((const uint8_t *)fp8_codes, (uint32_t)n, d.dim, ix->m_rowterm, ix->stream);
+            else e = launch_f32_row_norm2(staging, (uint32_t)n, d.ld, d.dim, ix->m_rowterm, ix->stream);
             if (e == hipSuccess) e = hipMemcpyAsync(h_n2.data(), ix->m_rowterm, n * 4, hipMemcpyDeviceToHost, ix->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(ix->stream);
         }
         (void)hipFree(staging);
         staging = nullptr;
         if (e != hipSuccess) return bail(fail(HVX_ERR_DEVICE, "fp8 row norms: %s", hipGetErrorString(e)));
-        for (float v : h_n2) ix->m_xmax2 = std::max(ix->m_xmax2, v);
+        if (d.metric != kCosine) // (code norms are no |x|^2: the maximum is an L2 quantity)
+            for (float v : h_n2) ix->m_xmax2 = std::max(ix->m_xmax2, v);
         ix->rowterm_rows = (uint32_t)n;
         d.vec8 = (const uint8_t *)fp8_codes;
         d.rowscale = fp8_scale;
@@ -1082,6 +1085,11 @@ int hvx::flat_scan_device(hvx_index *ix, const float *d_queries, uint32_t b, uin
                 if (timed) HIP_TRY(hipEventRecord(ix->ev1, ix->stream));
                 return HVX_OK;
             }
+            // the whole batch goes to the VALU scan: the path word keeps the flags of the attempts that ran before it
+            const uint32_t tried = ix->last_scan_path;
+            const int rv = flat_scan_valu(ix, d_queries, b, k, d_subset, n_rows, d_ids, d_scores, d_counts, d_status, timed, true);
+            ix->last_scan_path |= tried;
+            return rv;
         }
     }
     return flat_scan_valu(ix, d_queries, b, k, d_subset, n_rows, d_ids, d_scores, d_counts, d_status, timed, true);

@@ -10,7 +10,7 @@ struct MfmaArgs {
     const uint16_t *qhi, *qlo; // [bpad][dim]
     const uint32_t *subset;    // optional: scan position -> row (restricted scans); NULL = the rows themselves
     const void *rows;          // [n][dim] bf16, or fp8 codes
-    const float *rowscale;     // [n] fp8 only
+    const float *rowscale;     // [n] fp8 only; NULL for cosine over fp8 rows (rowterm = the codes' norms)
     const float *rowterm;      // [n]: |x|^2 (L2) or |x| (cosine)
     const float *qn2;          // [b]
     uint32_t dim, b, row0, nrows, metric;
@@ -87,6 +87,45 @@ __host__ __device__ inline float scan_error_bound(uint32_t kind, bool l2, uint32
     }
     return (l2 ? 2.0f * eps : eps) + 12.0f * (float)dim * 0x1p-24f + 0x1p-18f;
 }
+
+// ---- cosine: the magnitude precondition of the bound ----
+// scan_error_bound's cosine figure is relative to |q||x| and holds only while |q|^2, |q||x|, the dot product and every partial sum of the
+// contraction are normal f32 numbers.  Cosine has no component limit (the reference answers any finite magnitude through its f64
+// fallback), so the scans make the precondition true instead of assuming it:
+//   * the query: cosine is scale-invariant, so the contraction's copy of a cosine query (split_queries_kernel, split_queries_mx_kernel)
+//     is q^ = q 2^-e with max |q^_i| in [2^12, 2^13) -- an exact scaling -- and qn2 is |q^|^2: 2^12 <= |q^| < 2^13 sqrt(dim) <= 2^18.3
+//     (dim <= 1536) whatever |q| was.  The exact kernels (re-rank, tail, VALU) read the caller's query, never q^.
+//   * a row is TRUSTED when its norm header lies in [kCosTermMin, kCosTermMax] = [2^-100, 2^107].  Then every partial sum is at most
+//     |q^||x| < 2^126 (no overflow), and whatever a matrix core may flush -- products below 2^-126, at most dim 2^-126 in all, and row
+//     elements below 2^-126, at most sqrt(dim) 2^-126 of |x| -- is below 2^-27 |q^||x| and 2^-20 |q^||x|: inside the bound's 2^-18 term.
+//   * an UNTRUSTED row (an outlier whose norm overflows the product, a norm header clamped at FLT_MAX, a norm near the subnormals) and
+//     a non-finite dot product have no approximation: approx_half_cosine gives them 0, the smallest score there is.  Such a row
+//     passes every filter and is always among the candidates, where it is re-scored in the reference's order; it never moves the
+//     threshold the wrong way (a certificate whose (m+1)-th approximate score is 0 fails: more than m rows are untrusted -- the exact
+//     tail, the VALU scan or the next attempt answers, never a guess).
+//   * non-zero fp8 rows never leave the trusted range: x = scale codes, so cos(q, x) = cos(q, codes) and their scan divides the raw
+//     accumulator by |q^||codes| (fp8_code_norm_kernel; MfmaArgs.rowscale is NULL then): |codes| lies in [448, 448 sqrt(dim)].  An
+//     all-zero row (codes 0, scale 1) has |codes| = 0 and is untrusted.
+constexpr float kCosTermMin = 0x1p-100f, kCosTermMax = 0x1p107f;
+constexpr int kCosQueryExp = 12; // max |q^_i| in [2^12, 2^13)
+__host__ __device__ inline bool cosine_term_trusted(float term) { return term >= kCosTermMin && term <= kCosTermMax; }
+// exponent e of the exact scaling q^ = q 2^-e of a cosine query whose largest finite magnitude is mx (0: no scaling)
+__host__ __device__ inline int cosine_query_exponent(float mx) {
+    if (!(mx > 0.f)) return 0;
+    int ex;
+    (void)frexpf(mx, &ex); // mx = f 2^ex, f in [0.5, 1)
+    return ex - 1 - kCosQueryExp;
+}
+#if defined(__HIPCC__)
+// (1 - c) / 2 from the contraction's dot product, qn = |q^| and the row's norm header; 0 where there is no approximation (see above)
+__device__ __forceinline__ float approx_half_cosine(float dot, float qn, float term) {
+    if (!cosine_term_trusted(term) || !(__builtin_fabsf(dot) <= 3.4028234664e38f)) return 0.f;
+    const float den = qn * term;
+    float c = den > 0.f ? dot / den : 0.f; // (den = 0: a rejected query, masked to zeros; its scores are never reported)
+    c = c < -1.f ? -1.f : (c > 1.f ? 1.f : c);
+    return (1.0f - c) * 0.5f;
+}
+#endif
 
 // position of stored code `slot` (its index in the fp8 row) in the query operand of the 256 x 256 fp8 kernel: inside a
 // 64-code stage, MFMA step kk (0..3), lane half h, element e read code (2 (kk >> 1) + h) * 16 + (kk & 1) * 8 + e, so one

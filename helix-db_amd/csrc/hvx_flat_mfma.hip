@@ -17,6 +17,10 @@
 //      reference-order score >= t - E; if the k-th exact score is < t - E the answer is provably the
 //      exact scan's.  E = scan_error_bound (hvx_flat_mfma.h): what the contraction's rounded operands leave out plus the f32
 //      accumulation error of both orders, relative to (|q|^2 + max|x|^2)/2 for L2, absolute for cosine.
+//      Precondition: E is drawn around an f32 expression, so |q|^2, |q||x| and the dot product must be normal f32 numbers.  L2 has its
+//      component limit; cosine has none, so the cosine query is scaled by an exact power of two before it is split (step 1) and a row
+//      whose norm leaves [2^-100, 2^107] gets no approximate score at all: it counts as 0, is always a candidate and is re-scored
+//      (hvx_flat_mfma.h, "the magnitude precondition"; approx_half_cosine).  A certificate with t = 0 fails.
 //      Queries that fail are re-run with m = 1023; if that fails too they are reported, never guessed.
 #include <hip/hip_runtime.h>
 
@@ -54,6 +58,24 @@ __global__ __launch_bounds__(64) void bf16_row_norm2_kernel(const uint16_t *rows
     }
     for (int s = 32; s > 0; s >>= 1) acc += __shfl_xor(acc, s, 64);
     if (threadIdx.x == 0) out[r] = (float)acc;
+}
+
+// ---- fp8 rows under cosine: the norm of the row's CODES, sqrt(sum decode(code)^2).  x = scale code, so cos(q, x) = cos(q, codes): the scan
+// divides the raw accumulator by |q^||codes| and never forms scale x anything.  The largest code of a row is +-448 by construction of the
+// quantiser, so |codes| lies in [448, 448 sqrt(dim)] whatever the row's magnitude: a non-zero fp8 row has an approximation
+// (hvx_flat_mfma.h, "the magnitude precondition"), also where |x| itself overflows the norm header.  An all-zero row has codes 0 under
+// scale 1 (hvx_dtype.hip): its code norm is 0, outside the trusted range, and it is re-scored exactly like any untrusted row. ----
+__global__ __launch_bounds__(64) void fp8_code_norm_kernel(const uint8_t *codes, uint32_t n, uint32_t dim, float *out) {
+    const uint32_t r = blockIdx.x;
+    if (r >= n) return;
+    const uint8_t *p = codes + (size_t)r * dim;
+    double acc = 0.0;
+    for (uint32_t i = threadIdx.x; i < dim; i += 64) {
+        const double v = (double)fp8_e4m3_decode(p[i]);
+        acc += v * v;
+    }
+    for (int s = 32; s > 0; s >>= 1) acc += __shfl_xor(acc, s, 64);
+    if (threadIdx.x == 0) out[r] = (float)sqrt(acc);
 }
 
 // ---- bf16 shadow of f32 rows (plain element order): what the 256 x 256 kernel streams instead of the f32 rows ----
@@ -95,15 +117,29 @@ __global__ __launch_bounds__(256) void bf16_shadow_kernel(const float *rows, uin
 }
 
 // ---- queries: f32 -> bf16 hi + lo in the interleaved layout, padded with zero rows; |q|^2 ----
+// cosine != 0: the query is first scaled by the exact power of two that puts its largest magnitude into [2^12, 2^13) (hvx_flat_mfma.h,
+// "the magnitude precondition"): hi, lo and qn2 are those of the scaled query, so |q^|^2 and the dot products stay normal f32 numbers
+// for queries at 2^-100 as at 2^100.  L2 queries are bounded by the component limit and are split as they are.
 __global__ __launch_bounds__(64) void split_queries_kernel(const float *q, uint32_t b, uint32_t bpad, uint32_t dim,
                                                            uint16_t *qhi, uint16_t *qlo, float *qn2, uint32_t fp8_layout,
-                                                           uint16_t *qhi_tile8) {
+                                                           uint16_t *qhi_tile8, uint32_t cosine) {
     const uint32_t r = blockIdx.x;
     if (r >= bpad) return;
+    int qe = 0;
+    if (cosine && r < b) {
+        float mx = 0.f;
+        for (uint32_t i = threadIdx.x; i < dim; i += 64) {
+            const float v = q[(size_t)r * dim + i];
+            if (f32_is_finite(v)) mx = fmaxf(mx, fabsf(v));
+        }
+        for (int s = 32; s > 0; s >>= 1) mx = fmaxf(mx, __shfl_xor(mx, s, 64));
+        qe = cosine_query_exponent(mx);
+    }
     double acc = 0.0;
     for (uint32_t i = threadIdx.x; i < dim; i += 64) {
         float v = r < b ? q[(size_t)r * dim + i] : 0.f;
         if (!f32_is_finite(v)) v = 0.f; // rejected queries are masked by their status; keep the GEMM finite
+        if (qe) v = ldexpf(v, -qe);     // exact (an element 2^-138 of the largest or less may round: nothing next to |q^| >= 2^12)
         const uint16_t h = f32_to_bf16_rne(v);
         const float res = v - bf16_to_f32(h);
         const uint32_t s = fp8_layout == 2u ? i : (fp8_layout ? fp8_slot_of(i) : bf16_slot_of(i)); // 2: f32 rows, plain order
@@ -122,7 +158,12 @@ __global__ __launch_bounds__(64) void split_queries_kernel(const float *q, uint3
 // restore the magnitudes: q ~ s hi + (s / 16) lo with |q - that| <= 2^-9 |q| per element for normal pieces (3 mantissa bits twice; a
 // subnormal lo piece adds <= 2^-14 s <= 2^-21 max |q| absolute).  The certificate's bound: scan_error_bound(kErrMxFp8).  Layout: [query][dim / 64 stages][64 hi codes | 64 lo codes], element i at position fp8_slot_of(i) of the
 // row (the order the fp8 rows are stored in): a lane of the tile kernel reads 32 consecutive codes of a row and of a query.
-__global__ __launch_bounds__(64) void split_queries_mx_kernel(const float *q, uint32_t b, uint32_t bpad, uint32_t dim, unsigned char *qmx, uint32_t *qexp) {
+// The pieces are formed from q 2^-E (ldexpf: exact, and no 2^-E or 2^E that could leave the f32 range on its own).  cosine != 0: the block
+// scale is that of the scaled query q^ of split_queries_kernel -- max |q^| in [2^12, 2^13) puts it at 2^5 whatever |q| was, in step with the
+// qn2 the epilogue divides by.  L2: E is clamped to the E8M0 range of both pieces (queries below 2^-115 keep fewer bits: the component
+// limit bounds them above, and the re-rank decides below).
+__global__ __launch_bounds__(64) void split_queries_mx_kernel(const float *q, uint32_t b, uint32_t bpad, uint32_t dim, unsigned char *qmx, uint32_t *qexp,
+                                                              uint32_t cosine) {
     const uint32_t r = blockIdx.x;
     if (r >= bpad) return;
     float mx = 0.f;
@@ -137,19 +178,20 @@ __global__ __launch_bounds__(64) void split_queries_mx_kernel(const float *q, ui
         (void)frexpf(mx, &ex); // mx = f 2^ex, f in [0.5, 1): mx / 2^(ex - 9) in [256, 512) would overflow 448 -> one more
         e = ex - 8;            // mx / 2^e in [128, 256)
     }
-    e = e < -100 ? -100 : (e > 100 ? 100 : e);
-    const float inv = ldexpf(1.0f, -e), sc = ldexpf(1.0f, e);
+    if (!cosine) e = e < -100 ? -100 : (e > 100 ? 100 : e);
     for (uint32_t i = threadIdx.x; i < dim; i += 64) {
         float v = r < b ? q[(size_t)r * dim + i] : 0.f;
         if (!f32_is_finite(v)) v = 0.f;
-        const uint8_t hi = fp8_e4m3_encode(v * inv);
-        const float res = v - fp8_e4m3_decode(hi) * sc; // exact: both are multiples of the hi step, within f32's 24 bits
-        const uint8_t lo = fp8_e4m3_encode(res * inv * 16.0f);
+        const float vs = ldexpf(v, -e);
+        const uint8_t hi = fp8_e4m3_encode(vs);
+        const float res = vs - fp8_e4m3_decode(hi); // exact: both are multiples of the hi step, within f32's 24 bits
+        const uint8_t lo = fp8_e4m3_encode(res * 16.0f);
         const uint32_t s = fp8_slot_of(i), at = (s >> 6) * 128u + (s & 63u);
         qmx[(size_t)r * dim * 2 + at] = hi;
         qmx[(size_t)r * dim * 2 + at + 64u] = lo;
     }
-    if (threadIdx.x == 0) qexp[r] = (uint32_t)(127 + e);
+    // cosine: q^ = q 2^-(ex - 1 - kCosQueryExp) = 2^(e - ex + 1 + kCosQueryExp) (q 2^-e) = 2^(kCosQueryExp - 7) x the pieces' value
+    if (threadIdx.x == 0) qexp[r] = (uint32_t)(127 + (cosine ? (mx > 0.f ? kCosQueryExp - 7 : 0) : e));
 }
 
 // ---- the contraction ----
@@ -312,7 +354,7 @@ __global__ __launch_bounds__(256) void flat_mfma_bf16_kernel(MfmaArgs a) {
         if (rloc >= a.nrows) continue;
         const size_t node = a.subset ? a.subset[a.row0 + rloc] : a.row0 + rloc;
         const float term = a.rowterm[node];
-        const float rsc = FP8 ? a.rowscale[node] : 1.0f;
+        const float rsc = FP8 && a.rowscale ? a.rowscale[node] : 1.0f; // (cosine over fp8 rows: the term is the codes' norm, no scale)
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -325,10 +367,7 @@ __global__ __launch_bounds__(256) void flat_mfma_bf16_kernel(MfmaArgs a) {
                     s = (a.qn2[qq] + term) - 2.0f * dot;
                     s = s < 0.f ? 0.f : s;
                 } else {
-                    const float den = sqrtf(a.qn2[qq]) * term;
-                    float c = den > 0.f ? dot / den : 0.f;
-                    c = c < -1.f ? -1.f : (c > 1.f ? 1.f : c);
-                    s = (1.0f - c) * 0.5f;
+                    s = approx_half_cosine(dot, sqrtf(a.qn2[qq]), term);
                 }
                 if (FILT) {
                     if (s < thr_r[i][e]) { // rare once the threshold has settled: ~ (m+1) / rows-seen per row
@@ -356,10 +395,7 @@ __global__ __launch_bounds__(256) void flat_dots_to_scores_kernel(MfmaArgs a) {
         s = (a.qn2[q] + term) - 2.0f * dot;
         s = s < 0.f ? 0.f : s;
     } else {
-        const float den = sqrtf(a.qn2[q]) * term;
-        float c = den > 0.f ? dot / den : 0.f;
-        c = c < -1.f ? -1.f : (c > 1.f ? 1.f : c);
-        s = (1.0f - c) * 0.5f;
+        s = approx_half_cosine(dot, sqrtf(a.qn2[q]), term);
     }
     a.dist[(size_t)q * a.chunk_ld + i] = s;
 }
@@ -702,8 +738,17 @@ static hipError_t launch_rerank(const RerankArgs &a, uint32_t b, hipStream_t s) 
 // scan_error_bound evaluated by the host compiler, for the CPU tests that hold the bound to its numpy twin and to the adversarial fixtures
 // (tests/test_exact_bound_fixtures.py).  Not part of the C ABI (include/helix_vec.h).
 extern "C" float hvxi_scan_error_bound(uint32_t kind, uint32_t l2, uint32_t dim) { return hvx::scan_error_bound(kind, l2 != 0u, dim); }
+// the magnitude precondition's two host-evaluable pieces, for tests/test_magnitude_fixtures.py (not part of the C ABI either)
+extern "C" int hvxi_cosine_query_exponent(float mx) { return hvx::cosine_query_exponent(mx); }
+extern "C" uint32_t hvxi_cosine_term_trusted(float term) { return hvx::cosine_term_trusted(term) ? 1u : 0u; }
 
 namespace hvx {
+
+hipError_t launch_fp8_code_norm(const uint8_t *codes, uint32_t n, uint32_t dim, float *out, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(fp8_code_norm_kernel, dim3(n), dim3(64), 0, s, codes, n, dim, out);
+    return hipGetLastError();
+}
 
 hipError_t launch_bf16_row_norm2(const uint16_t *rows, uint32_t n, uint32_t dim, float *out, hipStream_t s) {
     if (n == 0) return hipSuccess;
@@ -712,7 +757,8 @@ hipError_t launch_bf16_row_norm2(const uint16_t *rows, uint32_t n, uint32_t dim,
 }
 
 static int flat_mfma_impl(hvx_index *ix, const float *d_queries, uint32_t b, uint32_t k, const uint32_t *d_subset, uint32_t n_rows,
-                          uint64_t *d_ids, float *d_scores, uint32_t *d_counts, uint32_t *d_status, bool timed, bool allow_filter);
+                          uint64_t *d_ids, float *d_scores, uint32_t *d_counts, uint32_t *d_status, bool timed, bool allow_filter,
+                          bool force_tail = false);
 
 // scan all rows of a bf16 index for b device-resident queries (see the file header)
 int flat_mfma_device(hvx_index *ix, const float *d_queries, uint32_t b, uint32_t k, const uint32_t *d_subset, uint32_t n_rows,
@@ -767,7 +813,8 @@ static int ensure_shadow(hvx_index *ix) {
 }
 
 static int flat_mfma_impl(hvx_index *ix, const float *d_queries, uint32_t b, uint32_t k, const uint32_t *d_subset, uint32_t n_rows,
-                          uint64_t *d_ids, float *d_scores, uint32_t *d_counts, uint32_t *d_status, bool timed, bool allow_filter) {
+                          uint64_t *d_ids, float *d_scores, uint32_t *d_counts, uint32_t *d_status, bool timed, bool allow_filter,
+                          bool force_tail) {
     const DevIndex &d = ix->dev;
     const uint32_t n = n_rows; // rows of the scan: the whole index, or the restricted row list
     if (k == 0) return fail(HVX_ERR_K_RANGE, "result count must be non-zero");
@@ -822,7 +869,7 @@ static int flat_mfma_impl(hvx_index *ix, const float *d_queries, uint32_t b, uin
         ix->rowterm_rows = d.n;
     }
     hipLaunchKernelGGL(split_queries_kernel, dim3(bpad), dim3(64), 0, ix->stream, d_queries, b, bpad, d.dim, ix->m_qhi, ix->m_qlo, ix->m_qn2,
-                       f32 ? 2u : (fp8 ? 1u : 0u), fp8 && tile_ok ? ix->m_qhi8 : nullptr);
+                       f32 ? 2u : (fp8 ? 1u : 0u), fp8 && tile_ok ? ix->m_qhi8 : nullptr, d.metric == kCosine ? 1u : 0u);
     HIP_TRY(hipGetLastError());
     // fp8 rows take the MX-scaled fp8 build of the tile kernel unless another build is asked for (4 = the bf16-widening two-workgroup build)
     const bool mx_build = fp8 && tile_ok && ix->opt[HVX_OPT_FLAT_TILE_BUILD] == 0u && d.dim % 128u == 0u;
@@ -832,7 +879,8 @@ static int flat_mfma_impl(hvx_index *ix, const float *d_queries, uint32_t b, uin
             if ((rc = ix->regrow((void **)&ix->m_qexp, (size_t)bpad * 4))) return rc;
             ix->cap_qmx = (size_t)bpad * d.dim;
         }
-        hipLaunchKernelGGL(split_queries_mx_kernel, dim3(bpad), dim3(64), 0, ix->stream, d_queries, b, bpad, d.dim, ix->m_qmx, ix->m_qexp);
+        hipLaunchKernelGGL(split_queries_mx_kernel, dim3(bpad), dim3(64), 0, ix->stream, d_queries, b, bpad, d.dim, ix->m_qmx, ix->m_qexp,
+                           d.metric == kCosine ? 1u : 0u);
         HIP_TRY(hipGetLastError());
     }
     if (timed) HIP_TRY(hipEventRecord(ix->ev0, ix->stream));
@@ -853,9 +901,34 @@ static int flat_mfma_impl(hvx_index *ix, const float *d_queries, uint32_t b, uin
     const bool skip_fast = ix->m_fast_misses >= 2 && (ix->m_fast_skipped++ % 32u) != 31u;
     // small batches with the one-launch exact tail (hvx_flat_tail.hip) always take the one-pass contraction: a loose bound only re-scores
     // more rows there, it never sends the scan round again
-    const bool tail_first = !fp8 && !ix->opt[HVX_OPT_FLAT_NO_TAIL] && ix->opt[HVX_OPT_FLAT_NO_SMALLB] != 1u && flat_tail_supported(ix, b, k, n) &&
-                            flat_smallb_supported(d.dim, b, f32 ? 2 : 0) && (size_t)((n + 3u) & ~3u) * b * 4 <= (512u << 20);
-    for (int attempt = (allow_fast && (!skip_fast || tail_first)) ? 0 : 1; attempt < 3; ++attempt) {
+    const bool tail_first = force_tail || (!fp8 && !ix->opt[HVX_OPT_FLAT_NO_TAIL] && ix->opt[HVX_OPT_FLAT_NO_SMALLB] != 1u && flat_tail_supported(ix, b, k, n) &&
+                            flat_smallb_supported(d.dim, b, f32 ? 2 : 0) && (size_t)((n + 3u) & ~3u) * b * 4 <= (512u << 20));
+    // bf16 rows have no VALU scan to fall back to: a scan whose last certificate is missed (more than 1023 rows within the bound of the
+    // k-th score, or without an approximation at all: hvx_flat_mfma.h) is answered by the exact tail in batches of <= 128 queries where
+    // that kernel serves the shape -- whatever the handle's path options say: they choose among exact paths, not between an answer and none
+    // (include/helix_vec.h: HVX_OPT_FLAT_NO_TAIL, HVX_OPT_FLAT_NO_SMALLB).  `can` is asked for the largest sub-batch, min(b, 128): neither
+    // test grows stricter with fewer queries (flat_tail_supported does not read b, smallb_passes needs less LDS for fewer query tiles), so
+    // a shorter last sub-batch, down to one query, is served as well.  fp8 rows have neither kernel and keep the error.
+    auto last_resort = [&](uint32_t failed, uint32_t first) -> int {
+        const uint32_t step = 128u;
+        const bool can = !force_tail && d.dtype == HVX_BF16 && flat_tail_supported(ix, std::min(b, step), k, n) &&
+                         flat_smallb_supported(d.dim, std::min(b, step), 0) && (size_t)((n + 3u) & ~3u) * std::min(b, step) * 4 <= (512u << 20);
+        if (!can)
+            return fail(HVX_ERR_INVARIANT, "exact-scan certificate failed for %u queries (first %u): more than 1023 rows within the "
+                        "error bound of the k-th score", failed, first);
+        uint32_t path = ix->last_scan_path;
+        for (uint32_t q0 = 0; q0 < b; q0 += step) {
+            const uint32_t bb = std::min(step, b - q0);
+            const int rc2 = flat_mfma_impl(ix, d_queries + (size_t)q0 * d.dim, bb, k, d_subset, n_rows, d_ids + (size_t)q0 * k, d_scores + (size_t)q0 * k,
+                                           d_counts + q0, d_status ? d_status + q0 : nullptr, false, true, true);
+            if (rc2) return rc2;
+            path |= ix->last_scan_path;
+        }
+        ix->last_scan_path = path;
+        if (timed) HIP_TRY(hipEventRecord(ix->ev1, ix->stream));
+        return HVX_OK;
+    };
+    for (int attempt = (force_tail || (allow_fast && (!skip_fast || tail_first))) ? 0 : 1; attempt < 3; ++attempt) {
         const bool full = attempt >= 1;
         const uint32_t m = attempt == 2 ? 1023u : m0;
         if (attempt == 2 && m0 >= 1023u) break;
@@ -865,7 +938,7 @@ static int flat_mfma_impl(hvx_index *ix, const float *d_queries, uint32_t b, uin
         // (a shadow that exists may be behind the rows: appended since, or a vector replaced in place by an upsert -- it catches up here)
         if (f32 && ix->m_shadow && !full && (rc = ensure_shadow(ix))) return rc;
         const int sb_kind = f32 ? ((ix->m_shadow && !full) ? 0 : 2) : (fp8 ? 1 : 0); // (the shadow has no lo parts: the full split reads the f32 rows)
-        const bool smallb = ix->opt[HVX_OPT_FLAT_NO_SMALLB] != 1u && flat_smallb_supported(d.dim, b, sb_kind) &&
+        const bool smallb = (force_tail || ix->opt[HVX_OPT_FLAT_NO_SMALLB] != 1u) && flat_smallb_supported(d.dim, b, sb_kind) &&
                             (size_t)((n + 3u) & ~3u) * b * 4 <= (512u << 20) && kc <= 1024u;
         constexpr uint32_t kSmallbCandCap = 8192; // 32 slices x kc <= 256 pairs per query
         const bool sb_radix = smallb && kc <= 256u; // (kc > 256: the widened attempt of bf16 rows keeps the sorted-pool selection)
@@ -902,8 +975,10 @@ static int flat_mfma_impl(hvx_index *ix, const float *d_queries, uint32_t b, uin
         MfmaArgs ma{};
         ma.qhi = ix->m_qhi; ma.qlo = ix->m_qlo; ma.subset = d_subset;
         ma.rows = f32 ? (const void *)d.vec : (fp8 ? (const void *)d.vec8 : (const void *)d.vecb);
-        ma.rowscale = d.rowscale;
-        ma.rowterm = d.metric == kL2 ? ix->m_rowterm : d.hdr;
+        // cosine over fp8 rows: the codes' norms (computed at import) and no row scale -- cos(q, scale codes) = cos(q, codes)
+        const bool code_cosine = fp8 && d.metric == kCosine;
+        ma.rowscale = code_cosine ? nullptr : d.rowscale;
+        ma.rowterm = (d.metric == kL2 || code_cosine) ? ix->m_rowterm : d.hdr;
         ma.qn2 = ix->m_qn2; ma.dim = d.dim; ma.b = b; ma.metric = d.metric; ma.dist = ix->f_dist; ma.chunk_ld = chunk;
         ma.thr = ix->m_thr; ma.cand_sc = ix->m_csc; ma.cand_id = ix->m_cid; ma.cand_cnt = ix->m_ccnt; ma.cand_cap = kCandCap;
         auto contraction = [&](uint32_t r0, uint32_t rows, bool filtered) -> hipError_t {
@@ -939,7 +1014,7 @@ static int flat_mfma_impl(hvx_index *ix, const float *d_queries, uint32_t b, uin
             (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ix->device);
             sa.dist = ix->f_dist; sa.chunk_ld = chunk;
             HIP_TRY(launch_flat_smallb(sa, sb_kind, full, (uint32_t)cus, ix->opt[HVX_OPT_FLAT_NO_SMALLB] == 2u ? 1u : 0u, ix->stream));
-            if (!full && !ix->opt[HVX_OPT_FLAT_NO_TAIL] && flat_tail_supported(ix, b, k, n)) {
+            if (!full && (force_tail || !ix->opt[HVX_OPT_FLAT_NO_TAIL]) && flat_tail_supported(ix, b, k, n)) {
                 // round 6: the approximate dot products become the exact answer in ONE more launch (hvx_flat_tail.hip): rows whose
                 // approximate score could be below the query's k-th exact score are re-scored in the reference's order -- no candidate
                 // count, no certificate, nothing to read back, never a second pass over the rows
@@ -1037,11 +1112,9 @@ static int flat_mfma_impl(hvx_index *ix, const float *d_queries, uint32_t b, uin
                 if (!cert[i]) ix->m_failed.push_back(i);
             return HVX_MFMA_FALLBACK;
         }
-        if (attempt == 2 || (attempt == 1 && m0 >= 1023u))
-            return fail(HVX_ERR_INVARIANT, "exact-scan certificate failed for %u queries (first %u): more than 1023 rows within the "
-                        "error bound of the k-th score", failed, first);
+        if (attempt == 2 || (attempt == 1 && m0 >= 1023u)) return last_resort(failed, first);
     }
-    return fail(HVX_ERR_INVARIANT, "exact-scan certificate failed after widening");
+    return last_resort(b, 0);
 }
 
 } // namespace hvx

@@ -490,10 +490,7 @@ __global__ __launch_bounds__(256) void flat_select_radix_kernel(SelectArgs a) {
                     s = (qn2 + term) - 2.0f * dot;
                     s = s < 0.f ? 0.f : s;
                 } else {
-                    const float den = qn * term;
-                    float c = den > 0.f ? dot / den : 0.f;
-                    c = c < -1.f ? -1.f : (c > 1.f ? 1.f : c);
-                    s = (1.0f - c) * 0.5f;
+                    s = approx_half_cosine(dot, qn, term);
                 }
                 if (!score_valid(s)) bad = 1; // Candidate::try_new rejects the score (model.rs:21-29)
                 else kbits = __float_as_uint(s);

@@ -176,7 +176,9 @@ __global__ __launch_bounds__(256) void flat_exact_tail_kernel(TailArgs a) {
                     float c = dot / den;
                     c = c < -1.f ? -1.f : (c > 1.f ? 1.f : c);
                     s = (1.0f - c) * 0.5f;
-                    if (!(den > 0.f) || !f32_is_normal(den)) s = -inf; // extreme norms: the reference's f64 fallback decides -- always re-scored
+                    // no approximation outside the magnitude precondition (hvx_flat_mfma.h; qn is the scaled query's norm): the reference's
+                    // f64 fallback decides -- always re-scored
+                    if (!(den > 0.f) || !f32_is_normal(den) || !cosine_term_trusted(term)) s = -inf;
                 }
                 if (!f32_is_finite(s) || !f32_is_finite(dot)) s = -inf; // never trust a non-finite approximation: the row is re-scored
             }

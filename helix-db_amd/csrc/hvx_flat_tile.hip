@@ -90,17 +90,20 @@ __device__ __forceinline__ void tile_epilogue(const MfmaArgs &a, f32x16 (&acc)[4
     }
     if (tid == 0) *sCnt = 0u;
     float alpha[2], nbeta[2];
+    bool untrusted[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const uint32_t rloc = r0 + (uint32_t)(wn * 64 + j * 32 + fr);
         alpha[j] = 0.f;
-        nbeta[j] = -inf; // rows past the end of the scan never pass
+        nbeta[j] = -inf; // rows past the end of the scan never pass (not even with a NaN accumulator: see the test below)
+        untrusted[j] = false;
         if (rloc < a.nrows) {
             const size_t node = a.subset ? a.subset[a.row0 + rloc] : (size_t)a.row0 + rloc;
             const float term = a.rowterm[node];
-            const float rsc = FP8 ? a.rowscale[node] : 1.0f;
+            const float rsc = FP8 && a.rowscale ? a.rowscale[node] : 1.0f; // (cosine over fp8 rows: the term is the codes' norm, no scale)
             if (a.metric == kL2) { alpha[j] = rsc; nbeta[j] = -0.5f * term; }
-            else { alpha[j] = term > 0.f ? rsc / term : 0.f; nbeta[j] = 0.f; }
+            else if (cosine_term_trusted(term)) { alpha[j] = rsc / term; nbeta[j] = 0.f; }
+            else { alpha[j] = 0.f; nbeta[j] = inf; untrusted[j] = true; } // no approximation for this row (hvx_flat_mfma.h): it passes for every query, the exact test below scores it 0
         }
     }
     __syncthreads();
@@ -112,7 +115,9 @@ __device__ __forceinline__ void tile_epilogue(const MfmaArgs &a, f32x16 (&acc)[4
             const float hq = sH[m];
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                if (__builtin_fmaf(acc[i][j][e], alpha[j], nbeta[j]) > hq) {
+                // an untrusted row passes for every real query, also where its dot product overflowed (0 x inf = NaN compares false);
+                // every other NaN -- the accumulator of a padding row -- stays out
+                if (__builtin_fmaf(acc[i][j][e], alpha[j], nbeta[j]) > hq || (untrusted[j] && hq < inf)) {
                     const uint32_t pos = atomicAdd(sCnt, 1u);
                     if (pos < (uint32_t)kWgList) {
                         sLv[pos] = acc[i][j][e];
@@ -133,16 +138,13 @@ __device__ __forceinline__ void tile_epilogue(const MfmaArgs &a, f32x16 (&acc)[4
         if (qq >= a.b || rloc >= a.nrows) continue;
         const size_t node = a.subset ? a.subset[a.row0 + rloc] : (size_t)a.row0 + rloc;
         const float term = a.rowterm[node];
-        const float dot = FP8 ? sLv[t] * a.rowscale[node] : sLv[t];
+        const float dot = FP8 && a.rowscale ? sLv[t] * a.rowscale[node] : sLv[t];
         float sc;
         if (a.metric == kL2) {
             sc = (a.qn2[qq] + term) - 2.0f * dot;
             sc = sc < 0.f ? 0.f : sc;
         } else {
-            const float den = sqrtf(a.qn2[qq]) * term;
-            float c = den > 0.f ? dot / den : 0.f;
-            c = c < -1.f ? -1.f : (c > 1.f ? 1.f : c);
-            sc = (1.0f - c) * 0.5f;
+            sc = approx_half_cosine(dot, sqrtf(a.qn2[qq]), term);
         }
         if (sc < a.thr[qq]) {
             const uint32_t pos = atomicAdd(&a.cand_cnt[qq], 1u);

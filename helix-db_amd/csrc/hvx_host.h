@@ -178,14 +178,14 @@ struct hvx_index {
     size_t cap_qmx = 0;
     uint16_t *m_shadow = nullptr;    // f32 rows: this handle's view of shared->shadow (set once it is complete)
     std::shared_ptr<hvx_image_shared> shared = std::make_shared<hvx_image_shared>(); // forks share their parent's
-    float *m_qn2 = nullptr, *m_rowterm = nullptr; // |q|^2 per query; |x|^2 per row
+    float *m_qn2 = nullptr, *m_rowterm = nullptr; // |q|^2 per query; per row: |x|^2 (L2), the norm of the row's codes (cosine over fp8 rows)
     uint32_t *m_cert = nullptr;
     // filtered-epilogue pipeline: running thresholds and the (score, row) pairs a filtered launch lets through
     float *m_thr = nullptr, *m_csc = nullptr;
     uint32_t *m_cid = nullptr, *m_ccnt = nullptr;
     size_t cap_cand = 0, cap_cand_b = 0;
     size_t cap_qsplit = 0;
-    float m_xmax2 = 0.f;
+    float m_xmax2 = 0.f;             // the largest |x|^2 (the L2 filters' margin); stays 0 under cosine over fp8 rows, where no kernel reads it
     uint32_t rowterm_rows = 0;       // rows m_rowterm / m_xmax2 cover
     uint64_t rowterm_epoch = 0;      // shared->vec_epoch they were computed at
     uint32_t m_fast_misses = 0, m_fast_skipped = 0; // consecutive scans whose one-pass attempt missed a certificate / scans that skipped it
@@ -287,6 +287,7 @@ int restricted_run_plan(hvx_index *ix, const float *queries, uint32_t b, uint32_
                         uint32_t n_rows, const uint32_t *d_samples, uint64_t *out_ids, float *out_scores, uint32_t *out_counts,
                         uint32_t *out_status, hvx_restricted_stats *rstats, hvx_stats *stats);
 hipError_t launch_bf16_row_norm2(const uint16_t *rows, uint32_t n, uint32_t dim, float *out, hipStream_t s);
+hipError_t launch_fp8_code_norm(const uint8_t *codes, uint32_t n, uint32_t dim, float *out, hipStream_t s); // cosine: sqrt(sum decode(code)^2) per row
 int flat_scan_host(hvx_index *ix, const float *queries, uint32_t b, uint32_t k, const uint32_t *d_subset,
                    uint32_t n_rows, uint64_t *out_ids, float *out_scores, uint32_t *out_counts,
                    uint32_t *out_status, hvx_stats *stats);

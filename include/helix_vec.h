@@ -149,7 +149,9 @@ enum hvx_option {
                                         matrix instruction (query as two e4m3 pieces); 1, 2, 3 = as 0 (1 and 2 chose 512-thread builds, since
                                         retired); 4 = as 0 but fp8 codes widened to bf16 (the round-2 build: the A/B switch) */
     HVX_OPT_FLAT_NO_SMALLB = 8,      /* 1: batches of <= 128 queries do not take the one-pass streaming kernels; 2: batches of <= 32 queries stay on
-                                        the register-fragment build (rows straight into MFMA operands) instead of the LDS-ring build */
+                                        the register-fragment build (rows straight into MFMA operands) instead of the LDS-ring build.
+                                        Exception, as for HVX_OPT_FLAT_NO_TAIL: a scan over bf16 rows whose last certificate attempt fails is
+                                        answered by the small-batch kernel + exact tail (batches of <= 128 queries) instead of HVX_ERR_INVARIANT */
     HVX_OPT_HNSW_PAIR = 9,           /* owner / gatherer kernel (an owner wavefront + 1 or 3 gatherer wavefronts per query): 0 = when the
                                         handle runs one query per SIMD (hvx_index_set_occupancy(1): one batch in flight), 1 = never,
                                         2 = always where it is built, 3 = always, with ONE gatherer even where three are built */
@@ -160,13 +162,19 @@ enum hvx_option {
     HVX_OPT_RESTRICTED_EXACT_MIB = 12, /* device plan of HVX_RESTRICTED_AUTO: candidate sets whose rows take at most this many MiB are scanned
                                         exactly; 0 = 1024 */
     HVX_OPT_FLAT_NO_TAIL = 13,       /* 1: small-batch matrix-core scans keep the selection / re-rank / certificate steps of rounds 3-5 instead of the
-                                        one-launch exact tail (csrc/hvx_flat_tail.hip) */
+                                        one-launch exact tail (csrc/hvx_flat_tail.hip).  The option chooses among exact paths, not between an answer
+                                        and none: over bf16 rows (which have no VALU scan) a scan whose widened certificate attempt still fails --
+                                        more than 1023 rows within the bound, or without an approximate cosine (norms outside [2^-100, 2^107]) --
+                                        is answered by the tail all the same, where it serves the shape; the path word then carries
+                                        HVX_PATH_WIDENED | HVX_PATH_EXACT_TAIL */
     HVX_OPT_HNSW_SHADOW_PRUNE = 14,  /* 1: strict squared-Euclidean searches over f32 rows read every frontier row in f32; 0 = once the beam holds ef
                                         entries, rows whose bf16-shadow lower bound exceeds the beam's worst entry are not read (same results) */
     HVX_OPT_COUNT = 15
 };
 int hvx_index_set_option(hvx_index *, uint32_t option, uint32_t value);
-/* which kernels the handle's last exact scan ran (bit flags) */
+/* which kernels the handle's last exact scan ran (bit flags).  The flags accumulate over the attempts of ONE scan: a matrix-core scan
+ * over f32 rows that ends in the VALU scan -- for its failing queries (HVX_PATH_VALU_FALLBACK_QUERIES) or for the whole batch
+ * (HVX_PATH_VALU) -- keeps the flags of the attempts before it; the word equals HVX_PATH_VALU only where no matrix-core attempt ran. */
 enum hvx_scan_path {
     HVX_PATH_VALU = 1, HVX_PATH_MFMA_128 = 2, HVX_PATH_TILE_256 = 4, HVX_PATH_FILTERED = 8, HVX_PATH_FULL_SPLIT = 16,
     HVX_PATH_VALU_FALLBACK_QUERIES = 32, HVX_PATH_WIDENED = 64,

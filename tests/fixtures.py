@@ -400,3 +400,200 @@ def certificate_trap_bound(rows: str, dim: int, mx: bool) -> float:
     if mx:
         return 0.25 * scan_error_bound(ERR_MX_FP8, True, dim)
     return scan_error_bound_before_fix(True, rows == "f32", True, dim)
+
+
+# ---- magnitude: the ends of the f32 range (test_magnitude_fixtures.py, test_gpu_magnitude.py) ----
+# Cosine has no component limit: the reference answers any finite magnitude through its f64 fallback.  The matrix-core scans form an
+# approximate cosine in f32 from |q|^2, the row norm and the dot product, which is worthless once one of them leaves the normal range.
+# All scalings are powers of two (np.ldexp): exact in f32, so a scaled cosine case has the ranking of its unit-scale twin.
+
+# (name, sq, sr, outlier scale or None, trap): trap = the unguarded f32 approximation (approx_half_cosine_model) breaks scan_error_bound
+COSINE_SCALES = [
+    ("unit", 0, 0, None, False),
+    ("r70", 0, 70, None, False),
+    ("mixed", 0, "mixed", None, False),       # per-row 2^-100 .. 2^100
+    ("q40r40", 40, 40, None, False),
+    ("q70", 70, 0, None, True),               # |q|^2 = inf
+    ("q63", 63, 0, None, True),
+    ("q100r-100", 100, -100, None, True),     # max |q| above 2^100: beyond the exponent clamp the MX query split had
+    ("q-100r100", -100, 100, None, True),     # ... and below 2^-100; |q|^2 = 0
+    ("q-80", -80, 0, None, True),             # |q|^2 = 0
+    ("q60r60", 60, 60, None, True),           # |q|^2 = inf, |q||x| = inf
+    ("q62r62", 62, 62, None, True),           # the dot product overflows too
+    ("q-78r40", -78, 40, None, True),         # |q|^2 a one-bit subnormal, |q||x| normal
+    ("q-77r40", -77, 40, None, True),
+    ("q-74", -74, 0, None, False),            # |q|^2 subnormal with ~10 bits: within the bound
+    ("outliers", 0, 0, 122, True),            # five rows x 2^122, the query's source row among them: |q||x| overflows for those alone
+    ("r126", 0, 126, None, True),             # the row norm exceeds FLT_MAX (unit components clipped to +-3.9: every element stays finite)
+    ("q-70r-70", -70, -70, None, True),       # every product q_i x_i is below the normal range
+]
+COSINE_SCALE = {c[0]: c for c in COSINE_SCALES}
+# the pairs kept on the large-batch paths
+COSINE_SCALES_LARGE = ["unit", "q70", "q-80", "q62r62", "q-78r40", "outliers"]
+# on top of those, for the MX-scaled fp8 build alone: queries past 2^+-100 (its query split clamped the block exponent there)
+COSINE_SCALES_MX = ["q100r-100", "q-100r100"]
+# L2 / L1: (name, kind): "limit" = uniform in +-0.99 component_limit(metric, dim); the others scale Gaussian clusters
+L2_SCALES = [("limit", None), ("tiny", -60), ("subnormal", -72)]
+N_OUTLIERS = 5
+# seed per (dim, rows) of the exact-scan tests: the f64 gap between rank 10 and rank 11 is >= 2^-12 (cosine absolute, L2 relative to the
+# 10th score) -- checked by test_magnitude_fixtures.py; the gap does not depend on the scaling
+MAGNITUDE_SEEDS = {(100, 3000): 1, (768, 3000): 3, (256, 3000): 9, (256, 17500): 1, (256, 6000): 1, (256, 20000): 3, (256, 66000): 3}
+
+
+def clustered_rows(dim: int, n: int, seed: int):
+    """16 Gaussian centres plus 0.5 sigma noise (the tile tests' corpus); the query is one row plus 5 % noise.
+    Returns (rows, query, the query's source row)."""
+    rng = np.random.default_rng(seed)
+    centres = rng.standard_normal((16, dim)).astype(np.float32)
+    data = (centres[rng.integers(0, 16, n)] + 0.5 * rng.standard_normal((n, dim))).astype(np.float32)
+    src = int(rng.integers(n // 2, n))
+    q = (data[src] + 0.05 * rng.standard_normal(dim)).astype(np.float32)
+    return data, q, src
+
+
+def mixed_row_scales(n: int, seed: int) -> np.ndarray:
+    return np.random.default_rng(seed + 977).integers(-100, 101, n).astype(np.int32)
+
+
+def scaled_case(dim: int, n: int, seed: int, sq, sr, outliers=None, src_min: int = 0, allow_flush: bool = False, clip=None):
+    """clustered_rows with the query times 2^sq and the rows times 2^sr (an int, "mixed", or one exponent per row); `outliers`: N_OUTLIERS
+    rows -- the query's source row among them -- times 2^outliers on top.  src_min: the source row is moved (swapped) to a position >= it.
+    clip: the unit-scale components are clipped to +-clip first (the query is drawn from the clipped row).
+    Asserts that the scaling was exact: nothing overflowed and nothing non-zero fell below the normal range (unless allow_flush).
+    Returns (rows, query, source row)."""
+    data, q, src = clustered_rows(dim, n, seed)
+    if clip is not None:
+        q = (q - data[src]).astype(np.float32)
+        data = np.clip(data, -clip, clip).astype(np.float32)
+        q = (q + data[src]).astype(np.float32)
+    if src < src_min:
+        to = src_min + (src * 7919) % (n - src_min)
+        data[[src, to]] = data[[to, src]]
+        src = to
+    e = mixed_row_scales(n, seed) if isinstance(sr, str) else np.broadcast_to(np.asarray(sr, np.int32), (n,)).copy()
+    if outliers is not None:
+        rng = np.random.default_rng(seed + 5)
+        rows = np.concatenate([[src], rng.choice(np.setdiff1d(np.arange(n), [src]), N_OUTLIERS - 1, replace=False)])
+        e[rows] += outliers
+    sd = np.ldexp(data, e[:, None]).astype(np.float32)
+    sqv = np.ldexp(q, sq).astype(np.float32)
+    tiny = np.finfo(np.float32).tiny
+    for a, b in ((data, sd), (q, sqv)):
+        assert np.isfinite(b).all()
+        if not allow_flush:
+            assert (np.abs(b[a != 0]) >= tiny).all()
+    return sd, sqv, src
+
+
+def cosine_clip(name: str):
+    return 3.9 if name == "r126" else None
+
+
+def cosine_case(name: str, dim: int, n: int, seed: int, src_min: int = 0, unit: bool = False):
+    """the named row of COSINE_SCALES; unit=True: its unit-scale twin (the same rows and query before the powers of two)"""
+    _, sq, sr, out, _ = COSINE_SCALE[name]
+    if unit:
+        return scaled_case(dim, n, seed, 0, 0, src_min=src_min, clip=cosine_clip(name))
+    return scaled_case(dim, n, seed, sq, sr, outliers=out, src_min=src_min, clip=cosine_clip(name))
+
+
+def limit_case(dim: int, n: int, seed: int, limit: float):
+    """rows and a query (one row plus 5 % noise, clipped) uniform in +-0.99 limit"""
+    rng = np.random.default_rng(seed)
+    lim = np.float32(0.99) * np.float32(limit)
+    data = (rng.uniform(-1.0, 1.0, (n, dim)).astype(np.float32) * lim).astype(np.float32)
+    src = int(rng.integers(n // 2, n))
+    q = np.clip(data[src] + (0.05 * rng.standard_normal(dim)).astype(np.float32) * lim, -lim, lim).astype(np.float32)
+    return data, q, src
+
+
+def l2_seed(name: str, dim: int, n: int) -> int:
+    """the seed whose rank-10 / rank-11 gap is >= 2^-12 of the 10th score and whose f32 top-10 is the f64 one (test_magnitude_fixtures.py):
+    uniform rows are nearly equidistant, so the limit case keeps a seed of its own"""
+    return 5 if name == "limit" else MAGNITUDE_SEEDS[(dim, n)]
+
+
+def l2_case(name: str, dim: int, n: int, seed: int, limit: float):
+    if name == "limit":
+        return limit_case(dim, n, seed, limit)
+    s = dict(L2_SCALES)[name]
+    return scaled_case(dim, n, seed, s, s)
+
+
+def _pow2_normalised(a: np.ndarray, axis=None):
+    """a / 2^floor(log2 max|a|) in f64 (exact), per row (axis=1) or whole: magnitudes in [0, 2)"""
+    a = np.asarray(a, np.float64)
+    m = np.abs(a).max(axis=axis, keepdims=axis is not None)
+    _, ex = np.frexp(np.where(m > 0, m, 1.0))
+    return np.ldexp(a, -(ex - 1)), ex - 1
+
+
+def f64_half_cosine(data: np.ndarray, q: np.ndarray) -> np.ndarray:
+    """(1 - cos) / 2 in f64, each operand first scaled by its own max-abs power of two: no overflow at any f32 magnitude"""
+    x, _ = _pow2_normalised(_f32(data), axis=1)
+    qq, _ = _pow2_normalised(_f32(q))
+    return (1.0 - (x @ qq) / (np.linalg.norm(x, axis=1) * np.linalg.norm(qq))) * 0.5
+
+
+def f64_l2sq(data: np.ndarray, q: np.ndarray) -> np.ndarray:
+    """|x - q|^2 in f64 with both operands scaled by ONE power of two (the larger max-abs), the scale restored in f64"""
+    x = _f32(data).astype(np.float64)
+    qq = _f32(q).astype(np.float64)
+    m = max(float(np.abs(x).max()), float(np.abs(qq).max()), np.finfo(np.float64).tiny)
+    e = math.frexp(m)[1] - 1
+    d = np.ldexp(x, -e) - np.ldexp(qq, -e)
+    return np.ldexp((d * d).sum(axis=1), 2 * e)
+
+
+def approx_half_cosine_model(data: np.ndarray, q: np.ndarray, flush: bool = False) -> np.ndarray:
+    """numpy twin of the f32 expression the matrix-core scans evaluated WITHOUT a magnitude guard: qn2 = fl32(|q|^2), term = fl32(|x|)
+    clamped to FLT_MAX, dot accumulated in f32 from f32 products; den = sqrtf(qn2) * term; c = den > 0 ? dot / den : 0, clamped to
+    [-1, 1]; (1 - c) / 2.  flush: a matrix core that flushes subnormal products and sums to zero (the scalar f32 operations keep
+    subnormals either way).  It shows which cases are traps; it is never the expected value of a device test."""
+    x = _f32(data)
+    qv = _f32(q)
+    fmax = np.finfo(np.float32).max
+    with np.errstate(all="ignore"):
+        qn2 = np.float32(min((qv.astype(np.float64) ** 2).sum(), np.inf))
+        xs, ex = _pow2_normalised(x, axis=1)
+        term = np.minimum(np.ldexp(np.linalg.norm(xs, axis=1), ex[:, 0]), fmax).astype(np.float32)
+        prod = (x * qv[None, :]).astype(np.float32)
+        if flush:
+            prod = np.where(np.abs(prod) < np.finfo(np.float32).tiny, np.float32(0), prod)
+        dot = prod.sum(axis=1, dtype=np.float32)
+        if flush:
+            dot = np.where(np.abs(dot) < np.finfo(np.float32).tiny, np.float32(0), dot)
+        den = (np.sqrt(qn2) * term).astype(np.float32)
+        c = np.where(den > 0, dot / den, np.float32(0)).astype(np.float32)
+        c = np.where(c < -1, np.float32(-1), np.where(c > 1, np.float32(1), c))
+        return ((np.float32(1) - c) * np.float32(0.5)).astype(np.float32)
+
+
+COS_TERM_MIN, COS_TERM_MAX, COS_QUERY_EXP = 2.0 ** -100, 2.0 ** 107, 12  # hvx_flat_mfma.h: kCosTermMin, kCosTermMax, kCosQueryExp
+
+
+def guarded_half_cosine_model(data: np.ndarray, q: np.ndarray, flush: bool = False):
+    """numpy twin of what the scans evaluate since the magnitude precondition (hvx_flat_mfma.h: approx_half_cosine over the scaled query of
+    split_queries_kernel): q^ = q 2^-e with max |q^_i| in [2^12, 2^13), qn2 = fl32(|q^|^2), the same f32 products and sums as
+    approx_half_cosine_model; rows whose norm header leaves [2^-100, 2^107] and non-finite dot products score 0.
+    Returns (scores, mask of the rows that HAVE an approximation)."""
+    x = _f32(data)
+    qv = _f32(q)
+    fmax = np.finfo(np.float32).max
+    mx = float(np.abs(qv).max())
+    e = math.frexp(mx)[1] - 1 - COS_QUERY_EXP
+    qh = np.ldexp(qv, -e).astype(np.float32)
+    with np.errstate(all="ignore"):
+        qn2 = np.float32((qh.astype(np.float64) ** 2).sum())
+        xs, ex = _pow2_normalised(x, axis=1)
+        term = np.minimum(np.ldexp(np.linalg.norm(xs, axis=1), ex[:, 0]), fmax).astype(np.float32)
+        prod = (x * qh[None, :]).astype(np.float32)
+        if flush:
+            prod = np.where(np.abs(prod) < np.finfo(np.float32).tiny, np.float32(0), prod)
+            prod = np.where(np.abs(x) < np.finfo(np.float32).tiny, np.float32(0), prod)  # subnormal row elements too
+        dot = prod.sum(axis=1, dtype=np.float32)
+        has = (term >= np.float32(COS_TERM_MIN)) & (term <= np.float32(COS_TERM_MAX)) & np.isfinite(dot)
+        c = (dot / (np.sqrt(qn2) * term)).astype(np.float32)
+        c = np.where(c < -1, np.float32(-1), np.where(c > 1, np.float32(1), c))
+        s = ((np.float32(1) - c) * np.float32(0.5)).astype(np.float32)
+    return np.where(has, s, np.float32(0)), has
