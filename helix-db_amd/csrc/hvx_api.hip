@@ -17,6 +17,7 @@
 
 #include "hvx_host.h"
 #include "hvx_flat_mfma.h"
+#include "hvx_hnsw_plan.h"
 
 using namespace hvx;
 

@@ -35,6 +35,7 @@
 
 #include "hvx_host.h"
 #include "hvx_graph_dev.h"
+#include "hvx_hnsw_plan.h"
 #include "hvx_build_dev.h"
 
 using namespace hvx;
@@ -1053,7 +1054,7 @@ extern "C" int hvx_index_build(const hvx_index_desc *desc, const uint64_t *node_
     const uint32_t efc = params->ef_construction ? params->ef_construction : 200u;
     if (desc->dtype != HVX_F32) return fail(HVX_ERR_UNSUPPORTED, "the device build reads f32 rows (import the built graph with a reduced-precision dtype afterwards)");
     if (m0 > 64u || m > 32u) return fail(HVX_ERR_UNSUPPORTED, "device build serves m0 <= 64 (m <= 32)");
-    if (std::max(efc, m0) + 32u > 832u) return fail(HVX_ERR_UNSUPPORTED, "device build serves ef_construction <= 800");
+    if (wave_build_need(std::max(efc, m0), std::max(efc, 2u * m)) > kBeamMax) return fail(HVX_ERR_UNSUPPORTED, "device build serves ef_construction <= 800");
     const uint32_t ef0 = std::max(efc, m0);
 
     // ---- the image: rows + EMPTY graph with rows sized for m0 / m (+ room for rows appended later: hvx_index_insert_batch) ----
@@ -1076,12 +1077,7 @@ extern "C" int hvx_index_build(const hvx_index_desc *desc, const uint64_t *node_
                           params->reserve_upper_rows);
     if (rc) return rc;
     auto bail = [&](int code) { hvx_index_free(ix); return code; };
-    HnswArgs probe{};
-    probe.ix = ix->dev;
-    probe.ef = ef0;
-    // the unrolled builds serve L2 / cosine, the AVX+FMA tree, dim in {128,...,1536}, ef_construction <= 352; everything else (any
-    // dimension, Manhattan, the scalar / AVX summation trees, ef_construction <= 800) takes the GENERIC build of the same kernel
-    if (!hnsw_wave_supported(probe) && (ix->dev.s0 > 64u || ix->dev.su > 64u))
+    if (!hnsw_wave_build_supported(ix->dev, ef0, std::max(efc, 2u * m)))
         return bail(fail(HVX_ERR_UNSUPPORTED, "device build serves neighbour rows of <= 64 ids"));
     if (stats) memset(stats, 0, sizeof(*stats));
     if (n == 0) { *out = ix; return HVX_OK; }
@@ -1132,7 +1128,7 @@ extern "C" int hvx_index_insert_batch(hvx_index *ix, const uint64_t *node_ids, c
     if (m0 > 64u || m > 32u) return fail(HVX_ERR_UNSUPPORTED, "device inserts serve m0 <= 64 (m <= 32)");
     if (d.s0 < m0 || d.su < m) return fail(HVX_ERR_UNSUPPORTED, "the image's neighbour rows are narrower than the degree limits (build it with hvx_index_build)");
     if (m0 > 32u && (d.s0 > 64u || d.su > 64u)) return fail(HVX_ERR_UNSUPPORTED, "device inserts with m0 > 32 serve neighbour rows of <= 64 ids");
-    if (std::max(efc, m0) + 32u > 832u) return fail(HVX_ERR_UNSUPPORTED, "device build serves ef_construction <= 800");
+    if (wave_build_need(std::max(efc, m0), std::max(efc, 2u * m)) > kBeamMax) return fail(HVX_ERR_UNSUPPORTED, "device build serves ef_construction <= 800");
     const uint64_t n0 = d.n;
     if (n0 + count > ix->cap_rows)
         return fail(HVX_ERR_CANDIDATE_LIMIT, "the image holds %llu of %llu rows: %u more do not fit (hvx_build_params.reserve_rows)", (unsigned long long)n0,
@@ -1149,10 +1145,8 @@ extern "C" int hvx_index_insert_batch(hvx_index *ix, const uint64_t *node_ids, c
     if (ix->up_rows_used + up_need > ix->cap_up_rows)
         return fail(HVX_ERR_CANDIDATE_LIMIT, "the image's upper-layer rows are exhausted (%llu + %llu > %llu: hvx_build_params.reserve_upper_rows)",
                     (unsigned long long)ix->up_rows_used, (unsigned long long)up_need, (unsigned long long)ix->cap_up_rows);
-    HnswArgs probe{};
-    probe.ix = d;
-    probe.ef = std::max(efc, m0);
-    if (!hnsw_wave_supported(probe) && (d.s0 > 64u || d.su > 64u)) return fail(HVX_ERR_UNSUPPORTED, "device build serves neighbour rows of <= 64 ids");
+    // (a bf16 image outside the unrolled shapes has no build search either: that one fails at its launch)
+    if (!hnsw_wave_build_supported(d, std::max(efc, m0), std::max(efc, 2u * m)) && (d.s0 > 64u || d.su > 64u)) return fail(HVX_ERR_UNSUPPORTED, "device build serves neighbour rows of <= 64 ids");
     hipStream_t s = ix->stream;
     // ---- the rows: upload into the spare capacity, validate, headers (nothing is visible yet: d.n still ends before them) ----
     float *vdst;

@@ -19,6 +19,7 @@
 
 #include "hvx_beam.h"
 #include "hvx_device.h"
+#include "hvx_hnsw_plan.h"
 #include "hvx_kernels.h"
 
 #ifdef HVX_TUNING
@@ -304,190 +305,81 @@ hipError_t launch_hnsw_search(const HnswArgs &a, uint32_t b, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// dispatch to the one-wavefront-per-query kernel (hvx_hnsw_wave.h)
+// dispatch to the one-wavefront-per-query kernel (hvx_hnsw_wave.h) and its owner / gatherer sibling (hvx_hnsw_pair.h): plan_wave()
+// (hvx_hnsw_plan.h) decides what a launch is; the table below says which translation unit holds that instantiation
 // ---------------------------------------------------------------------------------------------
-struct WaveGeom {
-    uint32_t log2cap;
-    uint32_t cap; // slots of the LDS visited table
-    size_t lds;
-    uint32_t occ;
-};
-hipError_t launch_hnsw_wave_occ2(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_occ2_bf16(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_build(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_build_occ2(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_build_gen(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_build_bf16(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s); // one-node inserts into bf16 images
-hipError_t launch_hnsw_wave_gen_cos(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_gen_l2(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_gen_l1(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_l2(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_cos(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_prof(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_l2_bf16(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_cos_bf16(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_l2_ad(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_cos_ad(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_l2_bf16_ad(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_cos_bf16_ad(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_occ2_l2_ad(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);   // non-strict arms, two queries per SIMD
-hipError_t launch_hnsw_wave_occ2_cos_ad(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_occ2_l2_bf16_ad(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_occ2_cos_bf16_ad(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_pair_l2(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);       // owner / gatherer kernel (hvx_hnsw_pair.h)
-hipError_t launch_hnsw_pair_cos(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_pair_l2_bf16(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_pair_cos_bf16(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_wide_l2(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);  // strict arm, beams of 448 / 832
-hipError_t launch_hnsw_wave_wide_cos(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_wide_l2_bf16(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_wide_cos_bf16(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-constexpr uint32_t kRngWords = 1024, kRngWordsOcc2 = 256; // LDS window of the query RNG (hvx_hnsw_wave.h)
+enum WaveFamily { kFamNarrow, kFamWide, kFamGeneric, kFamProf, kFamPair };
+constexpr int kAny = -1;
+// launcher | family | metric | bf16 rows | non-strict arms | queries per SIMD | build search
+#define HVX_WAVE_UNITS(X)                                                                                            \
+    X(launch_hnsw_wave_l2, kFamNarrow, kL2, 0, 0, 1, 0)                                                              \
+    X(launch_hnsw_wave_cos, kFamNarrow, kCosine, 0, 0, 1, 0)                                                         \
+    X(launch_hnsw_wave_l2_bf16, kFamNarrow, kL2, 1, 0, 1, 0)                                                         \
+    X(launch_hnsw_wave_cos_bf16, kFamNarrow, kCosine, 1, 0, 1, 0)                                                    \
+    X(launch_hnsw_wave_l2_ad, kFamNarrow, kL2, 0, 1, 1, 0)                                                           \
+    X(launch_hnsw_wave_cos_ad, kFamNarrow, kCosine, 0, 1, 1, 0)                                                      \
+    X(launch_hnsw_wave_l2_bf16_ad, kFamNarrow, kL2, 1, 1, 1, 0)                                                      \
+    X(launch_hnsw_wave_cos_bf16_ad, kFamNarrow, kCosine, 1, 1, 1, 0)                                                 \
+    X(launch_hnsw_wave_occ2, kFamNarrow, kAny, 0, 0, 2, 0)                                                           \
+    X(launch_hnsw_wave_occ2_bf16, kFamNarrow, kAny, 1, 0, 2, 0)                                                      \
+    X(launch_hnsw_wave_occ2_l2_ad, kFamNarrow, kL2, 0, 1, 2, 0)                                                      \
+    X(launch_hnsw_wave_occ2_cos_ad, kFamNarrow, kCosine, 0, 1, 2, 0)                                                 \
+    X(launch_hnsw_wave_occ2_l2_bf16_ad, kFamNarrow, kL2, 1, 1, 2, 0)                                                 \
+    X(launch_hnsw_wave_occ2_cos_bf16_ad, kFamNarrow, kCosine, 1, 1, 2, 0)                                            \
+    X(launch_hnsw_wave_wide_l2, kFamWide, kL2, 0, 0, kAny, 0) /* strict arm, beams of 448 / 832 entries */           \
+    X(launch_hnsw_wave_wide_cos, kFamWide, kCosine, 0, 0, kAny, 0)                                                   \
+    X(launch_hnsw_wave_wide_l2_bf16, kFamWide, kL2, 1, 0, kAny, 0)                                                   \
+    X(launch_hnsw_wave_wide_cos_bf16, kFamWide, kCosine, 1, 0, kAny, 0)                                              \
+    X(launch_hnsw_wave_gen_l2, kFamGeneric, kL2, 0, 1, 1, 0)                                                         \
+    X(launch_hnsw_wave_gen_cos, kFamGeneric, kCosine, 0, 1, 1, 0)                                                    \
+    X(launch_hnsw_wave_gen_l1, kFamGeneric, kL1, 0, 1, 1, 0)                                                         \
+    X(launch_hnsw_wave_build, kFamNarrow, kAny, 0, 0, 1, 1)                                                          \
+    X(launch_hnsw_wave_build_occ2, kFamNarrow, kAny, 0, 0, 2, 1)                                                     \
+    X(launch_hnsw_wave_build_bf16, kFamNarrow, kAny, 1, 0, 1, 1) /* one-node inserts into bf16 images */             \
+    X(launch_hnsw_wave_build_gen, kFamGeneric, kAny, 0, 0, 1, 1)                                                     \
+    X(launch_hnsw_wave_prof, kFamProf, kAny, 0, kAny, 1, 0) /* phase timing; non-strict arms in tuning builds only */ \
+    X(launch_hnsw_pair_l2, kFamPair, kL2, 0, 0, 1, 0)                                                                \
+    X(launch_hnsw_pair_cos, kFamPair, kCosine, 0, 0, 1, 0)                                                           \
+    X(launch_hnsw_pair_l2_bf16, kFamPair, kL2, 1, 0, 1, 0)                                                           \
+    X(launch_hnsw_pair_cos_bf16, kFamPair, kCosine, 1, 0, 1, 0)
 
-// wide beams (round 4): the strict arm on the unrolled shapes runs register beams of 448 / 832 entries too (hvx_hnsw_wave_wide*.hip:
-// ef up to 800 = the reference's restricted-path limit; search.rs:267-1067 itself has no limit, ef beyond that takes the general kernel)
-static uint32_t wave_beam_limit(const HnswArgs &a) { return (a.adaptive || a.build_nodes || a.prof) ? 384u : 832u; }
-bool hnsw_wave_supported(const HnswArgs &a) {
-    const DevIndex &ix = a.ix;
-    if (ix.metric != kL2 && ix.metric != kCosine) return false;
-    if (ix.fkernel != kKernelAvxFma) return false;
-    if (ix.dim % 32u != 0u || ix.dim_main != ix.dim || ix.ld != ix.dim) return false;
-    if (ix.dtype != HVX_F32 && ix.dtype != HVX_BF16) return false;
-    const uint32_t nk = ix.dim >> 5;
-    if (nk != 4 && nk != 8 && nk != 12 && nk != 16 && nk != 24 && nk != 32 && nk != 48) return false; // (12 = dim 384: round 6)
-    if (ix.s0 > 64 || ix.su > 64) return false;
-    if (a.ef + 32u > wave_beam_limit(a)) return false;
-    return true;
-}
+typedef hipError_t WaveUnitFn(const HnswArgs &a, uint32_t b, const WavePlan &p, hipStream_t s);
+#define X(fn, fam, metric, bf, ad, occ, build) WaveUnitFn fn;
+HVX_WAVE_UNITS(X)
+#undef X
+struct WaveUnit { WaveUnitFn *fn; WaveFamily family; int metric, bf, ad, occ, build; };
+#define X(fn, fam, metric, bf, ad, occ, build) {fn, fam, (int)metric, bf, ad, occ, build},
+static const WaveUnit kWaveUnits[] = {HVX_WAVE_UNITS(X)};
+#undef X
 
-// the GENERIC builds of the non-strict arms: any dimension, metric and summation tree over f32 rows; one id per lane still
-// bounds the neighbour rows at 64 ids, the register beam bounds ef at 800 (the restricted path's k limit)
-static bool hnsw_wave_generic_supported(const HnswArgs &a) {
-    const DevIndex &ix = a.ix;
-    if (ix.dtype != HVX_F32) return false;
-    if (ix.s0 > 64 || ix.su > 64) return false;
-    if (a.ef + 32u > 832u) return false;
-    return true;
-}
-bool hnsw_wave_adaptive_supported(const HnswArgs &a) { return hnsw_wave_supported(a) || hnsw_wave_generic_supported(a); }
-
-static hipError_t launch_hnsw_wave_once(const HnswArgs &a, uint32_t b, hipStream_t s) {
-    WaveGeom g;
-    // visited hash: 64 slots per beam entry (load factor ~0.15-0.3 at the measured ~10 distance evaluations
-    // per expansion); the kernel spills to the exact HBM bitmap beyond 3/4 full
-    g.log2cap = 11;
-    while ((1u << g.log2cap) < 64u * a.ef && g.log2cap < 15) ++g.log2cap;
-    const bool generic = a.adaptive && !hnsw_wave_supported(a);
-    if (generic && g.log2cap > 14) g.log2cap = 14; // 64 KiB table (two workgroups per CU); larger visited sets spill to the bitmap
-    if (a.build_nodes && g.log2cap > 13) g.log2cap = 13; // build searches (ef_construction ~200): keep four workgroups per CU
-    // the 448 / 832-entry register beams (hvx_hnsw_wave_wide*.hip): strict searches with ef 353..800, and the re-run of a 384-entry beam
-    const bool wide = !a.adaptive && !a.build_nodes && !a.prof && (a.ef + 32u > 384u || (a.only_flagged && a.ef + 32u > 192u));
-    // Unrolled builds: 8 192 slots (32 KiB) whatever the beam width -- FOUR wavefronts per CU, one per SIMD.  (Rounds 1-3 sized the
-    // table at 64 slots per beam entry: 64 KiB from ef = 129, 128 KiB from ef = 257, i.e. two / one wavefronts per CU, which is
-    // where the ef sweep lost its throughput; a search visits ~10 rows per expansion, ~14 slots per beam entry at 3/4 load.)  A
-    // query that visits more than 6 144 rows continues on the exact HBM bitmap.
-    if (!generic && g.log2cap > 13) g.log2cap = 13;
-    if (a.log2cap >= 7 && a.log2cap <= 15) g.log2cap = a.log2cap; // HVX_OPT_WAVE_LOG2CAP: a tiny table exercises the spill path
-    // 160 KiB / 4: exactly four resident wavefronts per CU, one per SIMD, each with the SIMD's whole register file.
-    // occ = 2 (a.occupancy): eight per CU, two per SIMD -- the table shrinks until query + frontier + table fit 20 KiB
-    bool build_generic = false; // build searches outside the unrolled shapes: the GENERIC build (one query per SIMD)
-    if (a.build_nodes) {
-        HnswArgs probe = a; // the beam of a build search holds max(ef_construction, 2 M) entries on every layer
-        probe.ef = a.ef > a.build_ef_upper ? a.ef : a.build_ef_upper;
-        build_generic = !hnsw_wave_supported(probe);
-    }
-    // (the wide beams have two-per-SIMD builds too; the one for bf16 rows at dim 1536 spills ~200 registers: it stays one per SIMD)
-    // Round 5: the non-strict arms (the production default, SearchParams::new(k): access/search/storage.rs:140-141) have two-per-SIMD builds
-    // as well -- f32 and bf16 rows, the unrolled shapes; their RNG window shrinks to 256 words so that the visited table keeps its size.
-    const bool ad_occ2 = a.adaptive && !generic; // f32 and bf16 rows, the unrolled shapes
-    g.occ = (a.occupancy == 2 && (!a.adaptive || ad_occ2) && !a.prof && !build_generic && !(wide && a.ix.dtype == HVX_BF16 && (a.ix.dim >> 5) == 48u)) ? 2u : 1u;
-    size_t fixed = 512 + (size_t)a.ix.ld * 4 + (a.adaptive ? (g.occ == 2 ? kRngWordsOcc2 : kRngWords) * 4 : 0);
-    g.cap = 1u << g.log2cap;
-    if (g.occ == 2) {
-        // the table takes what the 20 KiB of a half-SIMD wavefront leave (any multiple of 64 slots: the hash maps onto [0, cap) by a
-        // multiply-high, hvx_hnsw_wave.h) -- 4 224 slots at dim 768, 3 456 at dim 1536 where a power of two allowed 4 096 / 2 048
-        const size_t room = 20 * 1024 > fixed ? (20 * 1024 - fixed) / 4 / 64 * 64 : 0;
-        const bool forced = a.log2cap >= 7 && a.log2cap <= 15;
-        if (!(forced && g.cap <= room)) { // (HVX_OPT_WAVE_LOG2CAP: a tiny table exercises the spill path)
-            g.cap = (uint32_t)std::min<size_t>(room, 8192);
-            if (g.cap < 512) { // no room for a useful table next to the query: one query per SIMD
-                g.occ = 1;
-                g.cap = 1u << g.log2cap;
-                fixed = 512 + (size_t)a.ix.ld * 4 + (a.adaptive ? kRngWords * 4 : 0);
-            }
-        }
-    }
-    const size_t budget = g.occ == 2 ? 20 * 1024 : 40 * 1024;
-    const size_t need = (size_t)4 * g.cap + fixed;
-    g.lds = need < budget ? budget : need;
-    if (a.build_nodes) {
-        if (a.ix.dtype == HVX_BF16) return (build_generic || g.occ != 1u) ? hipErrorInvalidValue : launch_hnsw_wave_build_bf16(a, b, g, s);
-        if (build_generic) return launch_hnsw_wave_build_gen(a, b, g, s);
-        return g.occ == 2 ? launch_hnsw_wave_build_occ2(a, b, g, s) : launch_hnsw_wave_build(a, b, g, s);
-    }
-    // one batch in flight: two wavefronts per query (owner + gatherer); the strict arm, beams of 192 / 384 entries
-    if (a.pair && !a.adaptive && !a.prof && !a.only_flagged && !wide && g.occ == 1 && a.ef + 32u <= 384u) {
-        WaveGeom pg = g;
-        const size_t pneed = (size_t)4 * g.cap + 528 + (size_t)a.ix.ld * 4;
-        pg.lds = pneed < 40 * 1024 ? 40 * 1024 : pneed;
-        if (a.ix.dtype == HVX_BF16) return a.ix.metric == kL2 ? launch_hnsw_pair_l2_bf16(a, b, pg, s) : launch_hnsw_pair_cos_bf16(a, b, pg, s);
-        return a.ix.metric == kL2 ? launch_hnsw_pair_l2(a, b, pg, s) : launch_hnsw_pair_cos(a, b, pg, s);
-    }
-    if (wide) {
-        if (a.ix.dtype == HVX_BF16) return a.ix.metric == kL2 ? launch_hnsw_wave_wide_l2_bf16(a, b, g, s) : launch_hnsw_wave_wide_cos_bf16(a, b, g, s);
-        return a.ix.metric == kL2 ? launch_hnsw_wave_wide_l2(a, b, g, s) : launch_hnsw_wave_wide_cos(a, b, g, s);
-    }
-    if (g.occ == 2 && a.adaptive) {
-        if (a.ix.dtype == HVX_BF16) return a.ix.metric == kL2 ? launch_hnsw_wave_occ2_l2_bf16_ad(a, b, g, s) : launch_hnsw_wave_occ2_cos_bf16_ad(a, b, g, s);
-        return a.ix.metric == kL2 ? launch_hnsw_wave_occ2_l2_ad(a, b, g, s) : launch_hnsw_wave_occ2_cos_ad(a, b, g, s);
-    }
-    if (g.occ == 2) return a.ix.dtype == HVX_BF16 ? launch_hnsw_wave_occ2_bf16(a, b, g, s) : launch_hnsw_wave_occ2(a, b, g, s);
-    if (generic) {
-        switch (a.ix.metric) {
-        case kCosine: return launch_hnsw_wave_gen_cos(a, b, g, s);
-        case kL2: return launch_hnsw_wave_gen_l2(a, b, g, s);
-        default: return launch_hnsw_wave_gen_l1(a, b, g, s);
-        }
-    }
-    if (a.adaptive && a.prof) return launch_hnsw_wave_prof(a, b, g, s); // tuning builds only
-    if (a.adaptive) {
-        if (a.ix.dtype == HVX_BF16) return a.ix.metric == kL2 ? launch_hnsw_wave_l2_bf16_ad(a, b, g, s) : launch_hnsw_wave_cos_bf16_ad(a, b, g, s);
-        return a.ix.metric == kL2 ? launch_hnsw_wave_l2_ad(a, b, g, s) : launch_hnsw_wave_cos_ad(a, b, g, s);
-    }
-    if (a.prof) return launch_hnsw_wave_prof(a, b, g, s);
-    if (a.ix.dtype == HVX_BF16) return a.ix.metric == kL2 ? launch_hnsw_wave_l2_bf16(a, b, g, s) : launch_hnsw_wave_cos_bf16(a, b, g, s);
-    return a.ix.metric == kL2 ? launch_hnsw_wave_l2(a, b, g, s) : launch_hnsw_wave_cos(a, b, g, s);
+static hipError_t launch_wave_plan(const HnswArgs &a, uint32_t b, const WavePlan &p, hipStream_t s) {
+    if (!p.ok) return hipErrorInvalidValue;
+    const WaveFamily fam = p.pair ? kFamPair : p.prof ? kFamProf : p.nk == 0 ? kFamGeneric : p.r > 6 ? kFamWide : kFamNarrow;
+    auto is = [](int want, int have) { return want == kAny || want == have; };
+    for (const WaveUnit &u : kWaveUnits)
+        if (u.family == fam && is(u.metric, (int)p.metric) && is(u.bf, p.bf) && is(u.ad, p.ad) && is(u.occ, p.occ) && is(u.build, p.build))
+            return u.fn(a, b, p, s);
+    return hipErrorInvalidValue;
 }
 
 // The search launch + its re-run: a beam of 64*R entries holds ef + >= 32 of slack; a query that evicted an EQUAL-score
 // candidate past that slack (many duplicate vectors) may differ from the reference, so the kernel flags it, appends it to the
 // handle's re-run list, and a second launch -- whose workgroups leave at once beyond the end of the list -- searches the
 // listed queries again with the next beam size (unrolled strict builds 192 -> 384 -> 832, non-strict 192 -> 384, generic 192 ->
-// 448 -> 832).  Queries that overflow even that stay flagged (hvx_stats.tie_overflow_queries).
+// 448 -> 832: the ladders of hvx_hnsw_plan.h).  Queries that overflow even that stay flagged (hvx_stats.tie_overflow_queries).
 hipError_t launch_hnsw_wave(const HnswArgs &a0, uint32_t b, hipStream_t s) {
-    HnswArgs a = a0;
-    const bool generic = a.adaptive && !hnsw_wave_supported(a);
-    const uint32_t need = a.ef + 32u;
-    // a wider instantiation exists
-    const bool wider = generic ? need <= 448u : (a.adaptive ? need <= 192u : need <= 448u);
-    const bool rerun = !a.prof && !a.build_nodes && a.tie_flags && a.rerun_ctl && wider && !tuning_env("HVX_NO_RERUN");
+    HnswArgs a = a0, r;
+    const WavePlan p = plan_wave(a);
+    WavePlan rp;
+    const bool rerun = plan_wave_rerun(a, p, tuning_env("HVX_AD_RERUN_OCC1") != nullptr, &r, &rp) && !tuning_env("HVX_NO_RERUN");
     if (!rerun) a.rerun_ctl = nullptr; // the search launch lists nothing when nobody empties the list
-    hipError_t e = launch_hnsw_wave_once(a, b, s);
+    hipError_t e = launch_wave_plan(a, b, p, s);
     if (e != hipSuccess || !rerun) return e;
     auto reset_list = [&](hipError_t err) { // a failed launch leaves the list to nobody: empty it here (the kernel also ignores entries >= b)
         if (err != hipSuccess) (void)hipMemsetAsync(a.rerun_ctl, 0, 8, s);
         return err;
     };
-    HnswArgs r = a;
-    r.only_flagged = 1;
-    // the re-run's workgroups leave at once (unless duplicates overflowed a beam): give them the build that fits NEXT TO whatever is
-    // resident -- two per SIMD, 20 KiB of LDS -- wherever it exists (the strict unrolled builds).  A one-per-SIMD re-run needs a SIMD
-    // with nothing else on it: behind the batches of other lanes that is a wait of 0.2 ms (round 3), behind the batcher's lanes
-    // running the four-wavefront pair kernel it starved for tens of milliseconds (gpurun r04c: p99 47 ms).
-    if (!a.adaptive || (hnsw_wave_supported(a) && !tuning_env("HVX_AD_RERUN_OCC1"))) r.occupancy = 2;
-    // the re-run keeps the launch's register budget where the wider build exists for it (two queries per SIMD: its few wavefronts
-    // fit next to the resident batches of the other lanes); the 832-entry beams are one-per-SIMD builds
-    return reset_list(launch_hnsw_wave_once(r, b, s));
+    return reset_list(launch_wave_plan(r, b, rp, s));
 }
 
 } // namespace hvx

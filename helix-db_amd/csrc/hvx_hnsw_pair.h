@@ -354,40 +354,41 @@ __global__ __launch_bounds__(64 * (1 + G)) __attribute__((amdgpu_waves_per_eu(1 
     }
 }
 
-template <typename K> static hipError_t launch_pair_kernel(K kern, uint32_t threads, const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s) {
-    if (g.lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds);
+template <uint32_t METRIC, int R, int NK, bool BF, int G> static hipError_t launch_pair_kernel(const HnswArgs &a, uint32_t b, const WavePlan &p, hipStream_t s) {
+    if (!p.ok || !p.pair || p.metric != METRIC || p.r != R || p.nk != NK || p.bf != BF || p.g != G || p.threads != 64u * (1u + G)) return hipErrorInvalidValue;
+    const auto kern = hnsw_pair_kernel<METRIC, R, NK, BF, G>;
+    if (p.lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(kern, dim3(b), dim3(threads), g.lds, s, a, g.cap);
+    hipLaunchKernelGGL(kern, dim3(b), dim3(p.threads), p.lds, s, a, p.cap);
     return hipGetLastError();
 }
-// three gatherers where a row is <= 24 pieces per lane, else one
-template <uint32_t METRIC, int R, int NK, bool BF> static hipError_t launch_pair_g(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s) {
-    constexpr int NL = BF ? NK / 2 : NK;
-    if constexpr (NL <= 24) {
-        if (a.pair_gatherers != 1u) return launch_pair_kernel(hnsw_pair_kernel<METRIC, R, NK, BF, 3>, 256u, a, b, g, s);
+// three gatherers are built where a row is <= 24 pieces per lane, else one
+template <uint32_t METRIC, int R, int NK, bool BF> static hipError_t launch_pair_g(const HnswArgs &a, uint32_t b, const WavePlan &p, hipStream_t s) {
+    if constexpr ((BF ? NK / 2 : NK) <= 24) {
+        if (p.g == 3) return launch_pair_kernel<METRIC, R, NK, BF, 3>(a, b, p, s);
     }
-    return launch_pair_kernel(hnsw_pair_kernel<METRIC, R, NK, BF, 1>, 128u, a, b, g, s);
+    return launch_pair_kernel<METRIC, R, NK, BF, 1>(a, b, p, s);
 }
-
-template <uint32_t METRIC, int R, bool BF> static hipError_t launch_pair_nk(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s) {
-    switch (a.ix.dim >> 5) {
-    case 4: return launch_pair_g<METRIC, R, 4, BF>(a, b, g, s);
-    case 8: return launch_pair_g<METRIC, R, 8, BF>(a, b, g, s);
-    case 12: return launch_pair_g<METRIC, R, 12, BF>(a, b, g, s);
-    case 16: return launch_pair_g<METRIC, R, 16, BF>(a, b, g, s);
-    case 24: return launch_pair_g<METRIC, R, 24, BF>(a, b, g, s);
-    case 32: return launch_pair_g<METRIC, R, 32, BF>(a, b, g, s);
-    case 48: return launch_pair_g<METRIC, R, 48, BF>(a, b, g, s);
+template <uint32_t METRIC, int R, bool BF> static hipError_t launch_pair_nk(const HnswArgs &a, uint32_t b, const WavePlan &p, hipStream_t s) {
+    switch (p.nk) {
+    case 4: return launch_pair_g<METRIC, R, 4, BF>(a, b, p, s);
+    case 8: return launch_pair_g<METRIC, R, 8, BF>(a, b, p, s);
+    case 12: return launch_pair_g<METRIC, R, 12, BF>(a, b, p, s);
+    case 16: return launch_pair_g<METRIC, R, 16, BF>(a, b, p, s);
+    case 24: return launch_pair_g<METRIC, R, 24, BF>(a, b, p, s);
+    case 32: return launch_pair_g<METRIC, R, 32, BF>(a, b, p, s);
+    case 48: return launch_pair_g<METRIC, R, 48, BF>(a, b, p, s);
     default: return hipErrorInvalidValue;
     }
 }
-template <uint32_t METRIC, bool BF> static hipError_t launch_pair_r(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s) {
-    const uint32_t need = a.ef + 32u;
-    if (need <= 192) return launch_pair_nk<METRIC, 3, BF>(a, b, g, s);
-    if (need <= 384) return launch_pair_nk<METRIC, 6, BF>(a, b, g, s);
-    return hipErrorInvalidValue;
+template <uint32_t METRIC, bool BF> static hipError_t launch_pair(const HnswArgs &a, uint32_t b, const WavePlan &p, hipStream_t s) {
+    switch (p.r) {
+    case 3: return launch_pair_nk<METRIC, 3, BF>(a, b, p, s);
+    case 6: return launch_pair_nk<METRIC, 6, BF>(a, b, p, s);
+    default: return hipErrorInvalidValue;
+    }
 }
 
 } // namespace hvx

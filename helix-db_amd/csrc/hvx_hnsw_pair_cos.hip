@@ -2,7 +2,7 @@
 #include "hvx_hnsw_pair.h"
 
 namespace hvx {
-hipError_t launch_hnsw_pair_cos(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s) {
-    return launch_pair_r<kCosine, false>(a, b, g, s);
+hipError_t launch_hnsw_pair_cos(const HnswArgs &a, uint32_t b, const WavePlan &p, hipStream_t s) {
+    return launch_pair<kCosine, false>(a, b, p, s);
 }
 } // namespace hvx

@@ -2,7 +2,7 @@
 #include "hvx_hnsw_pair.h"
 
 namespace hvx {
-hipError_t launch_hnsw_pair_l2(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s) {
-    return launch_pair_r<kL2, false>(a, b, g, s);
+hipError_t launch_hnsw_pair_l2(const HnswArgs &a, uint32_t b, const WavePlan &p, hipStream_t s) {
+    return launch_pair<kL2, false>(a, b, p, s);
 }
 } // namespace hvx

@@ -27,6 +27,7 @@
 
 #include "hvx_beam.h"
 #include "hvx_device.h"
+#include "hvx_hnsw_plan.h"
 #include "hvx_kernels.h"
 #include "hvx_shadow_bound.h"
 
@@ -296,9 +297,7 @@ __device__ __forceinline__ void gather_consume(const DevIndex &ix, const float *
 // hands word (pos + rank) to the lane whose candidate is the rank-th one to draw.
 // RW = words of the LDS window: 1 024 (64 blocks, one per lane) for the one-query-per-SIMD builds; 256 (16 blocks, lanes 0..15) for
 // the two-per-SIMD builds, whose 20 KiB of LDS are better spent on the visited table -- the production-default parameters draw
-// ~120 words per query (profiles/history/r04s), a window is rarely refilled either way.
-constexpr uint32_t kRngWords = 1024;
-constexpr uint32_t kRngWordsOcc2 = 256;
+// ~120 words per query (profiles/history/r04s), a window is rarely refilled either way.  (kRngWords / kRngWordsOcc2: hvx_hnsw_plan.h)
 template <uint32_t RW> struct QueryRngT {
     static constexpr uint32_t kBlocks = RW / 16u;
     uint32_t *buf;   // LDS [RW], word w of the window at buf[(w % 16) * kBlocks + w / 16] (conflict-free fill)
@@ -1149,101 +1148,52 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) 
     hnsw_wave_query<METRIC, R, NK, BF, PROF, AD, ST, OCC, BUILD>(a, vcap, q);
 }
 
-// launch geometry shared by the per-metric translation units
-struct WaveGeom {
-    uint32_t log2cap;
-    uint32_t cap; // slots of the LDS visited table (1 << log2cap unless the launch sized it to fill its LDS budget)
-    size_t lds;
-    uint32_t occ; // wavefronts per SIMD the launch is budgeted for (1 or 2)
-};
-
-// per-metric launchers, defined in hvx_hnsw_wave_l2.hip / hvx_hnsw_wave_cos.hip / hvx_hnsw_wave_prof.hip
-hipError_t launch_hnsw_wave_l2(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_cos(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_l2_bf16(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_cos_bf16(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_prof(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-// two queries per SIMD (OCC = 2 builds), hvx_hnsw_wave_occ2.hip
-hipError_t launch_hnsw_wave_occ2(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_occ2_bf16(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-// search side of the device HNSW build (BUILD instantiations), hvx_hnsw_wave_build.hip
-hipError_t launch_hnsw_wave_build(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_build_gen(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s); // GENERIC build, hvx_hnsw_wave_build_gen.hip
-hipError_t launch_hnsw_wave_build_occ2(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s); // two per SIMD, hvx_hnsw_wave_build_occ2.hip
-// GENERIC builds (NK = 0) of the non-strict arms: any dim / metric / summation tree, ef <= 800; hvx_hnsw_wave_gen_*.hip
-hipError_t launch_hnsw_wave_gen_cos(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_gen_l2(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_gen_l1(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-// non-strict arms (AD instantiations), hvx_hnsw_wave_l2_ad.hip / hvx_hnsw_wave_cos_ad.hip
-hipError_t launch_hnsw_wave_l2_ad(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_cos_ad(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_l2_bf16_ad(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_cos_bf16_ad(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-// ... budgeted for two queries per SIMD (f32 rows), hvx_hnsw_wave_occ2_l2_ad.hip / hvx_hnsw_wave_occ2_cos_ad.hip
-hipError_t launch_hnsw_wave_occ2_l2_ad(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_occ2_cos_ad(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_occ2_l2_bf16_ad(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-hipError_t launch_hnsw_wave_occ2_cos_bf16_ad(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s);
-
-template <typename K> static hipError_t launch_wave_kernel(K kern, const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s) {
-    if (g.lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds);
+// The last step of every launch.  A translation unit only switches from the plan's runtime fields to the instantiation it holds; the
+// instantiation must BE the plan's, or nothing is launched (a plan mapped to the wrong unit fails instead of running another build).
+template <uint32_t METRIC, int R, int NK, bool BF, bool PROF = false, bool AD = false, bool ST = true, int OCC = 1, bool BUILD = false>
+static hipError_t launch_wave_kernel(const HnswArgs &a, uint32_t b, const WavePlan &p, hipStream_t s) {
+    if (!p.ok || p.pair || p.metric != METRIC || p.r != R || p.nk != NK || p.bf != BF || p.prof != PROF || p.ad != AD || p.st != ST || p.occ != OCC ||
+        p.build != BUILD || p.threads != 64u)
+        return hipErrorInvalidValue;
+    const auto kern = hnsw_wave_kernel<METRIC, R, NK, BF, PROF, AD, ST, OCC, BUILD>;
+    if (p.lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(kern, dim3(b), dim3(64), g.lds, s, a, g.cap);
+    hipLaunchKernelGGL(kern, dim3(b), dim3(64), p.lds, s, a, p.cap);
     return hipGetLastError();
 }
 
+// the unrolled shapes
 template <uint32_t METRIC, int R, bool BF, bool AD = false, bool ST = true, int OCC = 1, bool BUILD = false>
-static hipError_t launch_wave_nk(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s) {
-    switch (a.ix.dim >> 5) {
-    case 4: return launch_wave_kernel(hnsw_wave_kernel<METRIC, R, 4, BF, false, AD, ST, OCC, BUILD>, a, b, g, s);
-    case 8: return launch_wave_kernel(hnsw_wave_kernel<METRIC, R, 8, BF, false, AD, ST, OCC, BUILD>, a, b, g, s);
-    case 12: return launch_wave_kernel(hnsw_wave_kernel<METRIC, R, 12, BF, false, AD, ST, OCC, BUILD>, a, b, g, s); // dim 384 (round 6)
-    case 16: return launch_wave_kernel(hnsw_wave_kernel<METRIC, R, 16, BF, false, AD, ST, OCC, BUILD>, a, b, g, s);
-    case 24: return launch_wave_kernel(hnsw_wave_kernel<METRIC, R, 24, BF, false, AD, ST, OCC, BUILD>, a, b, g, s);
-    case 32: return launch_wave_kernel(hnsw_wave_kernel<METRIC, R, 32, BF, false, AD, ST, OCC, BUILD>, a, b, g, s);
-    case 48: return launch_wave_kernel(hnsw_wave_kernel<METRIC, R, 48, BF, false, AD, ST, OCC, BUILD>, a, b, g, s);
+static hipError_t launch_wave_nk(const HnswArgs &a, uint32_t b, const WavePlan &p, hipStream_t s) {
+    switch (p.nk) {
+    case 4: return launch_wave_kernel<METRIC, R, 4, BF, false, AD, ST, OCC, BUILD>(a, b, p, s);
+    case 8: return launch_wave_kernel<METRIC, R, 8, BF, false, AD, ST, OCC, BUILD>(a, b, p, s);
+    case 12: return launch_wave_kernel<METRIC, R, 12, BF, false, AD, ST, OCC, BUILD>(a, b, p, s); // dim 384 (round 6)
+    case 16: return launch_wave_kernel<METRIC, R, 16, BF, false, AD, ST, OCC, BUILD>(a, b, p, s);
+    case 24: return launch_wave_kernel<METRIC, R, 24, BF, false, AD, ST, OCC, BUILD>(a, b, p, s);
+    case 32: return launch_wave_kernel<METRIC, R, 32, BF, false, AD, ST, OCC, BUILD>(a, b, p, s);
+    case 48: return launch_wave_kernel<METRIC, R, 48, BF, false, AD, ST, OCC, BUILD>(a, b, p, s);
     default: return hipErrorInvalidValue;
     }
 }
-
-template <uint32_t METRIC, bool BF, bool AD = false, bool ST = true, int OCC = 1>
-static hipError_t launch_wave_r(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s) {
-    const uint32_t need = a.ef + 32u; // beam capacity 64*R must hold ef plus slack for equal-score evictions
-    if (need <= 192 && !a.only_flagged) return launch_wave_nk<METRIC, 3, BF, AD, ST, OCC>(a, b, g, s);
-    if (need <= 384) return launch_wave_nk<METRIC, 6, BF, AD, ST, OCC>(a, b, g, s); // also the re-run of an R = 3 launch: slack 32 -> 224+
+// ... with the two beams RA / RB this unit holds: the narrow ones (R 3 / 6) or the wide ones (R 7 / 13, one or two queries per SIMD:
+// the half-register build's second resident query hides the first one's round trips exactly as it does for the narrow beams)
+template <uint32_t METRIC, int RA, int RB, bool BF, bool AD = false, bool ST = true, int OCC = 1, bool BUILD = false>
+static hipError_t launch_wave_r(const HnswArgs &a, uint32_t b, const WavePlan &p, hipStream_t s) {
+    if (p.r == RA) return launch_wave_nk<METRIC, RA, BF, AD, ST, OCC, BUILD>(a, b, p, s);
+    if (p.r == RB) return launch_wave_nk<METRIC, RB, BF, AD, ST, OCC, BUILD>(a, b, p, s);
     return hipErrorInvalidValue;
 }
-// wide register beams of the strict arm (round 4; hvx_hnsw_wave_wide_*.hip): 448 entries (ef <= 416) and 832 entries (ef <= 800), one
-// query per SIMD; the 832-entry build is also the re-run of a 384- or 448-entry launch
-template <uint32_t METRIC, bool BF, int OCC> static hipError_t launch_wave_wide_o(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s) {
-    const uint32_t need = a.ef + 32u;
-    if (need <= 448 && !a.only_flagged) return launch_wave_nk<METRIC, 7, BF, false, true, OCC>(a, b, g, s);
-    if (need <= 832) return launch_wave_nk<METRIC, 13, BF, false, true, OCC>(a, b, g, s);
-    return hipErrorInvalidValue;
-}
-// one query per SIMD, or (handles with two queries per SIMD: several batches in flight) the half-register build, whose second
-// resident query hides the first one's round trips exactly as it does for the narrow beams
-template <uint32_t METRIC, bool BF> static hipError_t launch_wave_wide_r(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s) {
-    return g.occ == 2 ? launch_wave_wide_o<METRIC, BF, 2>(a, b, g, s) : launch_wave_wide_o<METRIC, BF, 1>(a, b, g, s);
-}
-// GENERIC build of the non-strict arms: beam of 64*R >= ef + 32 entries
-template <uint32_t METRIC, bool ST> static hipError_t launch_wave_gen_r(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s) {
-    const uint32_t need = a.ef + 32u;
-    if (need <= 192 && !a.only_flagged) return launch_wave_kernel(hnsw_wave_kernel<METRIC, 3, 0, false, false, true, ST>, a, b, g, s);
-    if (need <= 448 && !(a.only_flagged && need > 192)) return launch_wave_kernel(hnsw_wave_kernel<METRIC, 7, 0, false, false, true, ST>, a, b, g, s);
-    if (need <= 832) return launch_wave_kernel(hnsw_wave_kernel<METRIC, 13, 0, false, false, true, ST>, a, b, g, s);
-    return hipErrorInvalidValue;
-}
-template <uint32_t METRIC> static hipError_t launch_wave_gen(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s) {
-    return a.ad.stats ? launch_wave_gen_r<METRIC, true>(a, b, g, s) : launch_wave_gen_r<METRIC, false>(a, b, g, s);
-}
-// non-strict arms: with the per-query SearchStats of the filter / sampling stages when the caller asked for them,
-// else the diagnostics-free build
-template <uint32_t METRIC, bool BF>
-static hipError_t launch_wave_ad(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s) {
-    return a.ad.stats ? launch_wave_r<METRIC, BF, true, true>(a, b, g, s) : launch_wave_r<METRIC, BF, true, false>(a, b, g, s);
+// the GENERIC builds (NK = 0)
+template <uint32_t METRIC, bool AD, bool ST, bool BUILD> static hipError_t launch_wave_generic(const HnswArgs &a, uint32_t b, const WavePlan &p, hipStream_t s) {
+    switch (p.r) {
+    case 3: return launch_wave_kernel<METRIC, 3, 0, false, false, AD, ST, 1, BUILD>(a, b, p, s);
+    case 7: return launch_wave_kernel<METRIC, 7, 0, false, false, AD, ST, 1, BUILD>(a, b, p, s);
+    case 13: return launch_wave_kernel<METRIC, 13, 0, false, false, AD, ST, 1, BUILD>(a, b, p, s);
+    default: return hipErrorInvalidValue;
+    }
 }
 
 } // namespace hvx

@@ -5,16 +5,7 @@
 #include "hvx_hnsw_wave.h"
 
 namespace hvx {
-hipError_t launch_hnsw_wave_build_occ2(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s) {
-    if (a.ix.dtype != HVX_F32 || a.adaptive || !a.build_nodes) return hipErrorInvalidValue;
-    const uint32_t need = (a.ef > a.build_ef_upper ? a.ef : a.build_ef_upper) + 32u;
-    if (a.ix.metric == kL2) {
-        if (need <= 192) return launch_wave_nk<kL2, 3, false, false, true, 2, true>(a, b, g, s);
-        if (need <= 384) return launch_wave_nk<kL2, 6, false, false, true, 2, true>(a, b, g, s);
-    } else if (a.ix.metric == kCosine) {
-        if (need <= 192) return launch_wave_nk<kCosine, 3, false, false, true, 2, true>(a, b, g, s);
-        if (need <= 384) return launch_wave_nk<kCosine, 6, false, false, true, 2, true>(a, b, g, s);
-    }
-    return hipErrorInvalidValue;
+hipError_t launch_hnsw_wave_build_occ2(const HnswArgs &a, uint32_t b, const WavePlan &p, hipStream_t s) {
+    return p.metric == kL2 ? launch_wave_r<kL2, 3, 6, false, false, true, 2, true>(a, b, p, s) : launch_wave_r<kCosine, 3, 6, false, false, true, 2, true>(a, b, p, s);
 }
 } // namespace hvx

@@ -3,7 +3,7 @@
 #include "hvx_hnsw_wave.h"
 
 namespace hvx {
-hipError_t launch_hnsw_wave_gen_l2(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s) {
-    return launch_wave_gen<kL2>(a, b, g, s);
+hipError_t launch_hnsw_wave_gen_l2(const HnswArgs &a, uint32_t b, const WavePlan &p, hipStream_t s) {
+    return p.st ? launch_wave_generic<kL2, true, true, false>(a, b, p, s) : launch_wave_generic<kL2, true, false, false>(a, b, p, s);
 }
 } // namespace hvx

@@ -2,7 +2,7 @@
 #include "hvx_hnsw_wave.h"
 
 namespace hvx {
-hipError_t launch_hnsw_wave_l2_bf16(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s) {
-    return launch_wave_r<kL2, true>(a, b, g, s);
+hipError_t launch_hnsw_wave_l2_bf16(const HnswArgs &a, uint32_t b, const WavePlan &p, hipStream_t s) {
+    return launch_wave_r<kL2, 3, 6, true>(a, b, p, s);
 }
 } // namespace hvx

@@ -3,7 +3,7 @@
 #include "hvx_hnsw_wave.h"
 
 namespace hvx {
-hipError_t launch_hnsw_wave_l2_bf16_ad(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s) {
-    return launch_wave_ad<kL2, true>(a, b, g, s);
+hipError_t launch_hnsw_wave_l2_bf16_ad(const HnswArgs &a, uint32_t b, const WavePlan &p, hipStream_t s) {
+    return p.st ? launch_wave_r<kL2, 3, 6, true, true, true>(a, b, p, s) : launch_wave_r<kL2, 3, 6, true, true, false>(a, b, p, s);
 }
 } // namespace hvx

@@ -5,8 +5,7 @@
 #include "hvx_hnsw_wave.h"
 
 namespace hvx {
-hipError_t launch_hnsw_wave_occ2(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s) {
-    if (a.ix.dtype != HVX_F32 || a.adaptive) return hipErrorInvalidValue;
-    return a.ix.metric == kL2 ? launch_wave_r<kL2, false, false, true, 2>(a, b, g, s) : launch_wave_r<kCosine, false, false, true, 2>(a, b, g, s);
+hipError_t launch_hnsw_wave_occ2(const HnswArgs &a, uint32_t b, const WavePlan &p, hipStream_t s) {
+    return p.metric == kL2 ? launch_wave_r<kL2, 3, 6, false, false, true, 2>(a, b, p, s) : launch_wave_r<kCosine, 3, 6, false, false, true, 2>(a, b, p, s);
 }
 } // namespace hvx

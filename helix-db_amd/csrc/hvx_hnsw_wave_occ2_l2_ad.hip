@@ -5,8 +5,7 @@
 #include "hvx_hnsw_wave.h"
 
 namespace hvx {
-hipError_t launch_hnsw_wave_occ2_l2_ad(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s) {
-    if (a.ix.dtype != HVX_F32 || !a.adaptive) return hipErrorInvalidValue;
-    return a.ad.stats ? launch_wave_r<kL2, false, true, true, 2>(a, b, g, s) : launch_wave_r<kL2, false, true, false, 2>(a, b, g, s);
+hipError_t launch_hnsw_wave_occ2_l2_ad(const HnswArgs &a, uint32_t b, const WavePlan &p, hipStream_t s) {
+    return p.st ? launch_wave_r<kL2, 3, 6, false, true, true, 2>(a, b, p, s) : launch_wave_r<kL2, 3, 6, false, true, false, 2>(a, b, p, s);
 }
 } // namespace hvx

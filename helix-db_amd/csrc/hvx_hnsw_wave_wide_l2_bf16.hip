@@ -4,7 +4,7 @@
 #include "hvx_hnsw_wave.h"
 
 namespace hvx {
-hipError_t launch_hnsw_wave_wide_l2_bf16(const HnswArgs &a, uint32_t b, const WaveGeom &g, hipStream_t s) {
-    return launch_wave_wide_r<kL2, true>(a, b, g, s);
+hipError_t launch_hnsw_wave_wide_l2_bf16(const HnswArgs &a, uint32_t b, const WavePlan &p, hipStream_t s) {
+    return p.occ == 2 ? launch_wave_r<kL2, 7, 13, true, false, true, 2>(a, b, p, s) : launch_wave_r<kL2, 7, 13, true, false, true, 1>(a, b, p, s);
 }
 } // namespace hvx

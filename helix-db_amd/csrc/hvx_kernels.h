@@ -67,10 +67,8 @@ struct HnswArgs {
 size_t hnsw_lds_bytes(uint32_t ld);
 // general kernel (4 wavefronts per query, any metric/dim/summation tree); dirties the HBM bitmap
 hipError_t launch_hnsw_search(const HnswArgs &a, uint32_t b, hipStream_t s);
-// fast kernel (1 wavefront per query, hvx_hnsw_wave.h); leaves the HBM bitmap zeroed
-bool hnsw_wave_supported(const HnswArgs &a);
-// non-strict arms: the AD instantiations of the wave kernel (f32 rows only)
-bool hnsw_wave_adaptive_supported(const HnswArgs &a);
+// fast kernel (1 wavefront per query, hvx_hnsw_wave.h; launch_hnsw_wave below); leaves the HBM bitmap zeroed.  What it serves --
+// hnsw_wave_supported, hnsw_wave_adaptive_supported (the non-strict arms), hnsw_wave_build_supported -- is in hvx_hnsw_plan.h
 // SimHash of n device-resident f32 rows (row stride ld) against transposed hyperplanes [dim][64]
 hipError_t launch_simhash_rows(const float *planes_t, const float *rows, uint32_t dim, uint32_t ld, uint64_t n, uint64_t *out,
                                hipStream_t s);
