@@ -24,6 +24,10 @@
 // per lane and 64-bit masks: degree limits up to 32.  Limits up to 64 (the reference's scale fixture, M 32 / M0 64) run the kernels of
 // hvx_build_wide.hip -- two ids per lane, 128-bit masks, 128 search candidates per layer and node -- picked per index in insert_range;
 // their one-node steps are the one-wavefront kernels (f32 and bf16 rows); their batches hold half the fraction and do not overlap search and link.
+// bf16 images (hvx_index_build with dtype bf16, inserts, upserts, hvx_index_link_rows): the same loop over the packed rows.  The build search
+// takes the batch's rows widened to f32 as its queries (decode_rows_bf16_kernel), the BF builds of the select / link kernels widen bf16 rows
+// on their way into LDS (stage_row<BF>; build_link_wg_kernel<.., BF> in hvx_build_link_wg.h, instantiated in hvx_build_bf16.hip), the one-node
+// steps read them in place (pair_distance<.., BF>): every distance is the reference's on the ROUNDED vectors, bit for bit.
 // Round 3: the batched link step runs one WORKGROUP per link with the prune evaluated from LDS (build_link_wg_kernel below) and
 // the search side two wavefronts per SIMD for batches > 1 024 nodes: 1M x 768 in 4.1 s (round 2: 10.0 s).
 #include <hip/hip_runtime.h>
@@ -37,6 +41,7 @@
 #include "hvx_graph_dev.h"
 #include "hvx_hnsw_plan.h"
 #include "hvx_build_dev.h"
+#include "hvx_build_link_wg.h"
 
 using namespace hvx;
 
@@ -50,7 +55,7 @@ namespace hvx {
 
 
 // ---- step 2: the new node's own neighbour lists ----
-template <uint32_t METRIC, bool FUSED> __global__ __launch_bounds__(64) void build_select_kernel(BuildArgs a) {
+template <uint32_t METRIC, bool FUSED, bool BF> __global__ __launch_bounds__(64) void build_select_kernel(BuildArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const DevIndex &ix = a.ix;
     const uint32_t q = blockIdx.x, layer = blockIdx.y;
@@ -69,7 +74,7 @@ template <uint32_t METRIC, bool FUSED> __global__ __launch_bounds__(64) void bui
         L.csc[lane] = a.cand_sc[slot * kCand + lane];
     }
     __syncthreads();
-    const uint32_t ns = select_diverse_dev<METRIC, FUSED>(ix, L, hyd, maxn, lane);
+    const uint32_t ns = select_diverse_dev<METRIC, FUSED, BF>(ix, L, hyd, maxn, lane);
     if ((uint32_t)lane < ns) a.sel[slot * 32u + lane] = L.kept[lane];
     if (lane == 0) a.sel_cnt[slot] = ns;
     uint32_t stride;
@@ -94,7 +99,7 @@ __device__ __forceinline__ void remove_edge_dev(const BuildArgs &a, uint32_t lay
 }
 
 // ---- step 3: bidirectional links of the new node, in selection order, top layer first ----
-template <uint32_t METRIC, bool FUSED> __global__ __launch_bounds__(64) void build_link_kernel(BuildArgs a) {
+template <uint32_t METRIC, bool FUSED, bool BF> __global__ __launch_bounds__(64) void build_link_kernel(BuildArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const DevIndex &ix = a.ix;
     const uint32_t q = blockIdx.x;
@@ -125,7 +130,7 @@ template <uint32_t METRIC, bool FUSED> __global__ __launch_bounds__(64) void bui
             uint32_t dropped_id = kSentinel; // per lane: a candidate this prune removed
             if (nc > maxn) {
                 // rank the row's neighbours by distance to its owner, select_diverse with the owner as the reference point
-                stage_row(ix, L.qv, to, lane);
+                stage_row<BF>(ix, L.qv, to, lane);
                 const float thdr = ix.hdr[to];
                 __syncthreads();
                 if ((uint32_t)lane < nc) L.kept[lane] = v; // scratch: unsorted candidate ids
@@ -133,7 +138,7 @@ template <uint32_t METRIC, bool FUSED> __global__ __launch_bounds__(64) void bui
                 for (uint32_t p0 = 0; p0 < nc; p0 += 8) {
                     const uint32_t g = p0 + (uint32_t)grp;
                     const uint32_t other = L.kept[g < nc ? g : nc - 1u];
-                    const float d = group_distance<METRIC, FUSED>(ix, L.qv, thdr, other, j);
+                    const float d = staged_distance<METRIC, FUSED, BF>(ix, L.qv, thdr, other, j);
                     if (g < nc && j == 0) L.dtmp[g] = d;
                 }
                 __syncthreads();
@@ -147,7 +152,7 @@ template <uint32_t METRIC, bool FUSED> __global__ __launch_bounds__(64) void bui
                 __syncthreads();
                 if ((uint32_t)lane < nc) { L.cid[rank] = v; L.csc[rank] = dmine; }
                 __syncthreads();
-                const uint32_t keepn = select_diverse_dev<METRIC, FUSED>(ix, L, nc, maxn, lane);
+                const uint32_t keepn = select_diverse_dev<METRIC, FUSED, BF>(ix, L, nc, maxn, lane);
                 bool kept_mine = false;
                 for (uint32_t t = 0; t < keepn; ++t) kept_mine |= L.kept[t] == v;
                 if ((uint32_t)lane < nc && !kept_mine) dropped_id = v;
@@ -447,269 +452,6 @@ template <uint32_t METRIC, bool FUSED, bool BF> __global__ __launch_bounds__(102
     }
 }
 
-// ---- step 3, batched mode: one 256-thread workgroup per LINK (new node q, layer, selected neighbour s) ----
-// build_link_kernel walks a node's <= 32 links one after the other, and every prune inside it is a chain of ~100 dependent row
-// gathers (select_diverse stages candidate i, then scores it against the kept rows eight at a time, stops at the first hit):
-// 9.4 ms per 2 048-node batch, 70 % of the build (profiles/history/r02f).  In a batch the order in which links reach the graph is not
-// defined anyway, so every link gets its own workgroup, and the prune is evaluated EAGERLY from LDS: the nc <= Mmax + 1 rows of
-// the overflowing row and its owner's cross HBM once, and ALL pairwise distances among them (every pair independent of every
-// other: 561 pairs for 33 + 1 rows, eight per wavefront step) are computed with the reference's summation order -- the
-// distance is symmetric bit for bit (squares / products commute), so the pair set does not depend on the (score, id) order that
-// select_diverse walks.  The rows pass through LDS in COLUMN blocks of <= 256 floats: a pair's four AVX-lane accumulators are
-// carried in registers from block to block (each lane's fma chain runs over the depth in the same order as in one pass), the
-// next block is in flight in registers while this one is being used, and a workgroup holds ~46 KB of LDS: three per CU, so
-// the lock / row / store latencies of one link sit under the arithmetic of the others.  Then: owner distances -> Candidate order
-// (model.rs:55-61), P[i] bit j = D[c_i][c_j] < D[c_i][owner] (the test of mod.rs:832), and select_diverse + backfill
-// (mod.rs:809-856) is a walk over 64-bit masks: candidate i is diverse iff P[i] & kept == 0.  Same decisions as the lazy
-// evaluation, bit for bit.
-constexpr int kLinkTasks = 18; // wave-steps of 8 pairs per wavefront: 4 x 18 x 8 >= 561 pairs of 33 candidates + owner
-
-struct LinkLds {
-    float *rows;              // [ncmax + 1][ldp]: this column block of the candidate rows (row order of the neighbour row), then the owner's
-    float *D;                 // [ncmax + 1][ncmax + 1] pairwise distances (index nc = the owner)
-    uint32_t *cand;           // [64] ids in row order
-    uint32_t *cid;            // [64] ids sorted by (distance to the owner, id)
-    float *csc;               // [64] their distances
-    uint32_t *srow;           // [64] row index of sorted candidate r
-    unsigned long long *P;    // [64] predicate masks, sorted order
-    uint32_t *fin;            // [64] ids of the pruned row
-    uint32_t *sh;             // [8] nc, prune, present, overflow
-    unsigned char *pa, *pb;   // [pairs] the two rows of pair p
-};
-__device__ __host__ __forceinline__ size_t link_pairs_max(uint32_t ncmax) { return (size_t)(ncmax + 1u) * ncmax / 2u; }
-__device__ __forceinline__ LinkLds carve_link(char *smem, uint32_t ldp, uint32_t ncmax) {
-    LinkLds L;
-    L.rows = reinterpret_cast<float *>(smem);
-    char *p = smem + (size_t)(ncmax + 1u) * ldp * 4u;
-    L.P = reinterpret_cast<unsigned long long *>(p); p += 512;
-    L.D = reinterpret_cast<float *>(p); p += (size_t)(ncmax + 1u) * (ncmax + 1u) * 4u;
-    L.cand = reinterpret_cast<uint32_t *>(p); p += 256;
-    L.cid = reinterpret_cast<uint32_t *>(p); p += 256;
-    L.csc = reinterpret_cast<float *>(p); p += 256;
-    L.srow = reinterpret_cast<uint32_t *>(p); p += 256;
-    L.fin = reinterpret_cast<uint32_t *>(p); p += 256;
-    L.sh = reinterpret_cast<uint32_t *>(p); p += 32;
-    L.pa = reinterpret_cast<unsigned char *>(p); p += (link_pairs_max(ncmax) + 15u) & ~(size_t)15u;
-    L.pb = reinterpret_cast<unsigned char *>(p);
-    return L;
-}
-static size_t link_lds_bytes(uint32_t ldp, uint32_t ncmax) {
-    return (size_t)(ncmax + 1u) * ldp * 4u + 512u + (size_t)(ncmax + 1u) * (ncmax + 1u) * 4u + 5u * 256u + 32u +
-           2u * ((link_pairs_max(ncmax) + 15u) & ~(size_t)15u);
-}
-
-
-template <uint32_t METRIC, bool FUSED> __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void build_link_wg_kernel(BuildArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const DevIndex &ix = a.ix;
-    const uint32_t q = blockIdx.x >> 5, s = blockIdx.x & 31u, layer = blockIdx.y;
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, grp = lane >> 3, j = lane & 7;
-    const uint32_t me = a.nodes[q];
-    const uint32_t lv = ix.level[me];
-    const uint32_t top = lv < a.layers - 1u ? lv : a.layers - 1u;
-    if (layer > top) return;
-    const size_t slot = (size_t)layer * a.b + q;
-    if (s >= a.sel_cnt[slot]) return;
-    const uint32_t to = a.sel[slot * 32u + s];
-    const uint32_t maxn = layer == 0u ? a.m0 : a.m;
-    LinkLds L = carve_link(smem, a.ldp, a.ncmax);
-    uint32_t stride;
-    uint32_t *row = row_ptr(a, to, layer, stride);
-
-    // ---- add_bidirectional_link(from = me, to) (mutation.rs:1498-1583): append under the row owner's lock ----
-    if (wave == 0) {
-#ifdef HVX_TUNING
-        if (a.dbg && lane == 0) { // contention probe: how often the target's lock is found taken
-            uint32_t spins = 0;
-            while (__hip_atomic_load(&a.locks[to], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u && spins < 1000000u) { ++spins; __builtin_amdgcn_s_sleep(2); }
-            atomicAdd(&a.dbg[0], spins);
-        }
-#endif
-        lock_row_w(a.locks, to, lane);
-        uint32_t v = (uint32_t)lane < stride ? ld_row(row + lane) : kSentinel;
-        uint32_t deg = (uint32_t)__builtin_popcountll(__ballot(v != kSentinel));
-        const bool present = __ballot(v == me) != 0ull;
-        bool overflow = false;
-        if (!present) {
-            if (deg >= 64u) overflow = true;
-            else {
-                if ((uint32_t)lane == deg) v = me; // rows are canonical: the valid ids occupy lanes 0..deg-1
-                ++deg;
-            }
-        }
-        if (deg > maxn && deg > a.ncmax) overflow = true; // more rows than the LDS was sized for: cannot happen on rows this build wrote
-        L.cand[lane] = v;
-        if (lane == 0) {
-            L.sh[0] = deg;
-            L.sh[1] = (deg > maxn && !overflow) ? 1u : 0u;
-            L.sh[2] = present ? 1u : 0u;
-            L.sh[3] = overflow ? 1u : 0u;
-            if (overflow) *a.err = 1u;
-        }
-    }
-    __syncthreads();
-    const uint32_t nc = L.sh[0];
-    if (L.sh[1] == 0u) { // no prune: the appended id takes its place in the canonical row
-        if (wave == 0) {
-            if (L.sh[2] == 0u && L.sh[3] == 0u) store_canonical_w(row, stride, L.cand, nc, lane);
-            unlock_row_w(a.locks, to, lane);
-            if (lane == 0) HVX_DBG_ADD(a, 3, 1);
-        }
-        return;
-    }
-
-    // ---- all pairwise distances among the nc candidate rows and the owner's row (index nc) ----
-    const uint32_t nrows = nc + 1u, npairs = nrows * nc / 2u;
-    if ((uint32_t)tid >= 1u && (uint32_t)tid < nrows) { // pair p = b (b - 1) / 2 + a  <->  rows a < b
-        const uint32_t b = (uint32_t)tid, base = b * (b - 1u) / 2u;
-        for (uint32_t aa = 0; aa < b; ++aa) { L.pa[base + aa] = (unsigned char)aa; L.pb[base + aa] = (unsigned char)b; }
-    }
-    const uint32_t nk = ix.dim_main >> 5;                 // 32-float chunks of a row (dim == dim_main == ld: the host checked)
-    const uint32_t ck = a.link_ck;                        // chunks per column block (even)
-    const uint32_t nblocks = (nk + ck - 1u) / ck;
-    const uint32_t w4 = ck * 8u;                          // float4 per row and block
-    constexpr int kPre = 9;                               // float4 a thread carries for the next block: 34 rows x 64 float4 / 256 threads
-    float4 pre[kPre];
-#pragma unroll
-    for (int u = 0; u < kPre; ++u) pre[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-    auto prefetch = [&](uint32_t blk) __attribute__((always_inline)) {
-        const uint32_t c0 = blk * w4, cw = (nk - blk * ck < ck ? nk - blk * ck : ck) * 8u;
-#pragma unroll
-        for (int u = 0; u < kPre; ++u) {
-            const uint32_t e = (uint32_t)tid + 256u * (uint32_t)u;
-            const uint32_t r = e / w4, c = e - r * w4;
-            if (r < nrows && c < cw) {
-                const uint32_t node = r < nc ? L.cand[r] : to;
-                pre[u] = reinterpret_cast<const float4 *>(ix.vec + (size_t)node * ix.ld)[c0 + c];
-            }
-        }
-    };
-    auto commit = [&](uint32_t blk) __attribute__((always_inline)) {
-        const uint32_t cw = (nk - blk * ck < ck ? nk - blk * ck : ck) * 8u;
-#pragma unroll
-        for (int u = 0; u < kPre; ++u) {
-            const uint32_t e = (uint32_t)tid + 256u * (uint32_t)u;
-            const uint32_t r = e / w4, c = e - r * w4;
-            if (r < nrows && c < cw) reinterpret_cast<float4 *>(L.rows + (size_t)r * a.ldp)[c] = pre[u];
-        }
-    };
-    float4 acc[kLinkTasks];
-#pragma unroll
-    for (int t = 0; t < kLinkTasks; ++t) acc[t] = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int slot4 = chunk_slot(j);
-    prefetch(0);
-    if (tid < 64) L.P[tid] = 0ull;
-    for (uint32_t blk = 0; blk < nblocks; ++blk) {
-        commit(blk);
-        __syncthreads(); // block blk is in LDS (first round: and the pair table)
-        if (blk + 1u < nblocks) prefetch(blk + 1u); // in flight underneath the arithmetic
-        const uint32_t ckb = nk - blk * ck < ck ? nk - blk * ck : ck;
-#pragma unroll
-        for (int t = 0; t < kLinkTasks; ++t) {
-            const uint32_t p = ((uint32_t)wave + 4u * (uint32_t)t) * 8u + (uint32_t)grp;
-            if (((uint32_t)wave + 4u * (uint32_t)t) * 8u >= npairs) continue; // uniform in the wavefront
-            const uint32_t pp = p < npairs ? p : npairs - 1u;
-            const float4 *qp = reinterpret_cast<const float4 *>(L.rows + (size_t)L.pa[pp] * a.ldp) + slot4;
-            const float4 *rp = reinterpret_cast<const float4 *>(L.rows + (size_t)L.pb[pp] * a.ldp) + slot4;
-            float4 ac = acc[t];
-#pragma unroll 4
-            for (uint32_t k = 0; k < ckb; ++k) {
-                const float4 x = rp[k * 8u];
-                const float4 qq = qp[k * 8u];
-                if (METRIC == kL2) {
-                    const float d0 = qq.x - x.x, d1 = qq.y - x.y, d2 = qq.z - x.z, d3 = qq.w - x.w;
-                    if (FUSED) {
-                        ac.x = __builtin_fmaf(d0, d0, ac.x); ac.y = __builtin_fmaf(d1, d1, ac.y);
-                        ac.z = __builtin_fmaf(d2, d2, ac.z); ac.w = __builtin_fmaf(d3, d3, ac.w);
-                    } else {
-                        ac.x = d0 * d0 + ac.x; ac.y = d1 * d1 + ac.y;
-                        ac.z = d2 * d2 + ac.z; ac.w = d3 * d3 + ac.w;
-                    }
-                } else {
-                    if (FUSED) {
-                        ac.x = __builtin_fmaf(qq.x, x.x, ac.x); ac.y = __builtin_fmaf(qq.y, x.y, ac.y);
-                        ac.z = __builtin_fmaf(qq.z, x.z, ac.z); ac.w = __builtin_fmaf(qq.w, x.w, ac.w);
-                    } else {
-                        ac.x = qq.x * x.x + ac.x; ac.y = qq.y * x.y + ac.y;
-                        ac.z = qq.z * x.z + ac.z; ac.w = qq.w * x.w + ac.w;
-                    }
-                }
-            }
-            acc[t] = ac;
-        }
-        __syncthreads(); // everybody is done with block blk before the next one overwrites it
-    }
-#pragma unroll
-    for (int t = 0; t < kLinkTasks; ++t) {
-        const uint32_t p = ((uint32_t)wave + 4u * (uint32_t)t) * 8u + (uint32_t)grp;
-        if (((uint32_t)wave + 4u * (uint32_t)t) * 8u >= npairs) continue;
-        float r = avx_tree_reduce(acc[t]); // every lane of the group takes part
-        if (p < npairs) {
-            const uint32_t ra = L.pa[p], rb = L.pb[p];
-            if (METRIC == kCosine) {
-                const uint32_t na = ra < nc ? L.cand[ra] : to, nb = rb < nc ? L.cand[rb] : to;
-                r = cosine_finish(r, ix.hdr[na], ix.hdr[nb], ix.vec + (size_t)na * ix.ld, ix.vec + (size_t)nb * ix.ld, ix.dim);
-            }
-            if (j == 0) { L.D[ra * nrows + rb] = r; L.D[rb * nrows + ra] = r; }
-        }
-    }
-    __syncthreads();
-
-    // ---- rank the row's neighbours by distance to its owner (Candidate order: score, then id; model.rs:55-61) ----
-    if ((uint32_t)tid < nc) {
-        const float dmine = L.D[nc * nrows + (uint32_t)tid];
-        const uint32_t v = L.cand[tid];
-        uint32_t rank = 0;
-        for (uint32_t t = 0; t < nc; ++t) {
-            const float dt = L.D[nc * nrows + t];
-            const uint32_t it = L.cand[t];
-            rank += (dt < dmine || (dt == dmine && it < v)) ? 1u : 0u;
-        }
-        L.cid[rank] = v;
-        L.csc[rank] = dmine;
-        L.srow[rank] = (uint32_t)tid;
-    }
-    __syncthreads();
-    if (wave != 0) return;
-    // ---- P[i] bit jj = dist(c_i, c_jj) < dist(c_i, owner), jj < i in sorted order (strict <: mod.rs:832) ----
-    if ((uint32_t)lane < nc) {
-        const uint32_t ri = L.srow[lane];
-        const float si = L.csc[lane];
-        unsigned long long bits = 0ull;
-        for (uint32_t jj = 0; jj < (uint32_t)lane; ++jj)
-            if (L.D[ri * nrows + L.srow[jj]] < si) bits |= 1ull << jj;
-        L.P[lane] = bits;
-    }
-    wave_sync();
-
-    // ---- select_diverse + backfill over the masks (mod.rs:809-856); all lanes walk the same chain ----
-    unsigned long long kept = 0ull;
-    uint32_t ns = 0;
-    for (uint32_t i = 0; i < nc && ns < maxn; ++i)
-        if ((L.P[i] & kept) == 0ull) { kept |= 1ull << i; ++ns; }
-    for (uint32_t i = 0; i < nc && ns < maxn; ++i)
-        if (((kept >> i) & 1ull) == 0ull) { kept |= 1ull << i; ++ns; }
-    const bool have = (uint32_t)lane < nc;
-    const uint32_t mine = have ? L.cid[lane] : kSentinel;
-    const bool in = have && ((kept >> lane) & 1ull) != 0ull;
-    const unsigned long long im = __ballot(in);
-    if (in) L.fin[__builtin_popcountll(im & ((1ull << lane) - 1ull))] = mine;
-    const uint32_t dropped_id = (have && !in) ? mine : kSentinel;
-    wave_sync();
-    store_canonical_w(row, stride, L.fin, ns, lane);
-    unlock_row_w(a.locks, to, lane);
-    // every neighbour dropped by the prune loses its edge to `to` as well (mutation.rs:1890-1908): the graph stays symmetric
-    unsigned long long dm = __ballot(dropped_id != kSentinel);
-    while (dm) {
-        const uint32_t src = (uint32_t)__builtin_ctzll(dm);
-        dm &= dm - 1ull;
-        const uint32_t x = __builtin_amdgcn_readlane(dropped_id, src);
-        remove_edge_w(a, layer, x, to, lane);
-        if (lane == 0) HVX_DBG_ADD(a, 2, 1);
-    }
-    if (lane == 0) HVX_DBG_ADD(a, 1, 1);
-}
-
 template <typename K> static hipError_t launch_build(K kern, dim3 grid, const BuildArgs &a, hipStream_t s) {
     const size_t lds = build_lds_bytes(a.ix.ld);
     hipLaunchKernelGGL(kern, grid, dim3(64), lds, s, a);
@@ -732,21 +474,37 @@ __global__ void iota_kernel(uint32_t *p, uint32_t count, uint32_t first, uint32_
     if (i < count) p[i] = stride == 1u ? first + i : (uint32_t)(((unsigned long long)(first + i) * stride) % mod);
 }
 
+// the build searches of a bf16 batch read the nodes' ROUNDED vectors as f32 queries: rows nodes[0 .. count) of the image, widened into
+// out[count][dim] in plain order, one 16-byte piece per thread
+__global__ void decode_rows_bf16_kernel(const uint16_t *vecb, const uint32_t *nodes, uint32_t count, uint32_t dim, float *out) {
+    const uint32_t ppr = dim >> 3; // pieces per row
+    const size_t e = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (e >= (size_t)count * ppr) return;
+    const uint32_t i = (uint32_t)(e / ppr), t = (uint32_t)(e - (size_t)i * ppr);
+    const uint4 x = reinterpret_cast<const uint4 *>(vecb + (size_t)nodes[i] * dim)[t];
+    const uint32_t w[4] = {x.x, x.y, x.z, x.w};
+    float lo[4], hi[4];
+    bf16_piece_widen(w, lo, hi);
+    float *dst = out + (size_t)i * dim + bf16_piece_dst(t);
+    *reinterpret_cast<float4 *>(dst) = make_float4(lo[0], lo[1], lo[2], lo[3]);
+    *reinterpret_cast<float4 *>(dst + 32) = make_float4(hi[0], hi[1], hi[2], hi[3]);
+}
+
 // one instantiation per (metric, summation tree): the reference picks both per index (spaces/*.rs, distance/*.rs)
-using BuildKernel = void (*)(BuildArgs);
 struct BuildKernels {
     BuildKernel select, link, link_wg; // link_wg: null where the workgroup kernel has no instantiation (Manhattan)
     BuildKernel select_seq, link_seq;  // one node per step
 };
 template <uint32_t METRIC, bool FUSED> static BuildKernels build_kernels_of() {
-    BuildKernels k{build_select_kernel<METRIC, FUSED>, build_link_kernel<METRIC, FUSED>, nullptr, build_select_seq_kernel<METRIC, FUSED, false>,
+    BuildKernels k{build_select_kernel<METRIC, FUSED, false>, build_link_kernel<METRIC, FUSED, false>, nullptr, build_select_seq_kernel<METRIC, FUSED, false>,
                    build_link_seq_kernel<METRIC, FUSED, false>};
-    if constexpr (METRIC != kL1) k.link_wg = build_link_wg_kernel<METRIC, FUSED>;
+    if constexpr (METRIC != kL1) k.link_wg = build_link_wg_kernel<METRIC, FUSED, false>;
     return k;
 }
-// bf16 images (round 6): one node at a time only -- the many-workgroup select / link steps over the interleaved bf16 rows
+// bf16 images (L2 / cosine, the AVX+FMA tree: what the import accepts): every step reads the interleaved bf16 rows in place
 template <uint32_t METRIC> static BuildKernels build_kernels_bf16() {
-    return BuildKernels{nullptr, nullptr, nullptr, build_select_seq_kernel<METRIC, true, true>, build_link_seq_kernel<METRIC, true, true>};
+    return BuildKernels{build_select_kernel<METRIC, true, true>, build_link_kernel<METRIC, true, true>, build_link_wg_bf16_kernel(METRIC),
+                        build_select_seq_kernel<METRIC, true, true>, build_link_seq_kernel<METRIC, true, true>};
 }
 static BuildKernels pick_build_kernels(uint32_t metric, bool fused, bool bf16 = false) {
     if (bf16) return metric == kL2 ? build_kernels_bf16<kL2>() : build_kernels_bf16<kCosine>();
@@ -756,6 +514,9 @@ static BuildKernels pick_build_kernels(uint32_t metric, bool fused, bool bf16 = 
 }
 
 } // namespace hvx
+
+// hvx_build_params.sequential: HVX_BUILD_ONE_NODE (and any value the header does not name) = one node per batch
+static bool one_node_batches(const hvx_build_params *p) { return p->sequential != HVX_BUILD_AUTO && p->sequential != HVX_BUILD_BATCHED; }
 
 extern "C" void hvx_build_params_default(hvx_build_params *p) {
     if (!p) return;
@@ -773,7 +534,8 @@ extern "C" void hvx_build_params_default(hvx_build_params *p) {
 // been returned yet).
 static int insert_range(hvx_index *ix, uint64_t first, uint64_t count, const uint16_t *levels_in, uint64_t level_row0, const hvx_build_params *params,
                         uint32_t stride, uint64_t mod, hvx_build_stats *stats, const float *build_q = nullptr) {
-    // build_q (bf16 images): the nodes' ROUNDED vectors as f32 [count][dim] on the device -- the queries of their build searches
+    // build_q (bf16 images): the nodes' ROUNDED vectors as f32 [count][dim] on the device -- the queries of their build searches; null:
+    // every batch's rows are widened from the image into the call's scratch on the search stream
     if (count == 0) return HVX_OK;
     struct LevelOf { // levels_in[0] is the level of row level_row0
         const uint16_t *p;
@@ -797,7 +559,7 @@ static int insert_range(hvx_index *ix, uint64_t first, uint64_t count, const uin
     const uint32_t layers_max = top_level + 1u;
     uint32_t *d_iota, *d_locks, *d_cnt, *d_sel, *d_selcnt, *d_status, *d_err, *d_tick;
     uint64_t *d_cids;
-    float *d_csc, *d_gdm;
+    float *d_csc, *d_gdm, *d_bq = nullptr;
     // Round 6: the scratch, the link stream and its events stay with the handle (a one-node insert / upsert paid nine hipMalloc + hipFree --
     // each a device synchronisation --, a stream and four events per call: ~2 ms of a 6.4-ms upsert).  Only tuning buffers are per call.
     // Round 4: the search of batch i + 1 runs on the handle's stream WHILE batch i is selected and linked on a second stream.  Batch i + 1
@@ -824,13 +586,15 @@ static int insert_range(hvx_index *ix, uint64_t first, uint64_t count, const uin
     // degree limits above 32: twice the candidates and selected neighbours per layer and node, and the kernels of hvx_build_wide.hip
     const bool wide = std::max(m0, m) > 32u;
     const uint32_t kc = wide ? kCandWide : kCand, selw = wide ? kSelWide : 32u;
+    const bool bf16 = d.dtype == HVX_BF16;
     const size_t sz_cids = (size_t)layers_max * bmax * kc, sz_cnt = (size_t)layers_max * bmax, sz_sel = (size_t)layers_max * bmax * selw;
     int rc;
     {
         auto up = [](size_t b) { return (b + 255u) & ~(size_t)255u; };
         const size_t b_iota = up(count * 4), b_cids = up(2 * sz_cids * 8), b_csc = up(2 * sz_cids * 4), b_cnt = up(2 * sz_cnt * 4), b_sel = up(2 * sz_sel * 4),
-                     b_status = up((size_t)bmax * 4), b_err = 256, b_tick = up(2 * 64 * 4), b_gdm = up((size_t)layers_max * kSeqLayerDm * 4);
-        const size_t need = b_iota + b_cids + b_csc + 2 * b_cnt + b_sel + b_status + b_err + b_tick + b_gdm;
+                     b_status = up((size_t)bmax * 4), b_err = 256, b_tick = up(2 * 64 * 4), b_gdm = up((size_t)layers_max * kSeqLayerDm * 4),
+                     b_bq = (bf16 && !build_q) ? up((size_t)bmax * d.dim * 4) : 0;
+        const size_t need = b_iota + b_cids + b_csc + 2 * b_cnt + b_sel + b_status + b_err + b_tick + b_gdm + b_bq;
         if (need > ix->ins_cap) {
             ix->ins_cap = 0;
             if ((rc = ix->regrow(&ix->ins_scratch, need + need / 4))) return rc;
@@ -847,7 +611,8 @@ static int insert_range(hvx_index *ix, uint64_t first, uint64_t count, const uin
         d_sel = reinterpret_cast<uint32_t *>(p); p += b_sel;
         d_status = reinterpret_cast<uint32_t *>(p); p += b_status;
         d_err = reinterpret_cast<uint32_t *>(p); p += b_err;
-        d_gdm = reinterpret_cast<float *>(p);
+        d_gdm = reinterpret_cast<float *>(p); p += b_gdm;
+        if (b_bq) d_bq = reinterpret_cast<float *>(p);
         const uint64_t lock_rows = std::max<uint64_t>(rows_total, ix->cap_rows);
         if (lock_rows > ix->ins_locks_rows) { // one lock per row the image can hold: all zero between calls (every lock taken is released)
             ix->ins_locks_rows = 0;
@@ -883,13 +648,12 @@ static int insert_range(hvx_index *ix, uint64_t first, uint64_t count, const uin
     const uint32_t ldp = link_ck * 32u + 32u;
     const size_t link_lds = link_lds_bytes(ldp, ncmax);
     // serves rows without a scalar tail (dim % 32 == 0, no padding) and <= 33 candidates (561 pairs = 4 wavefronts x 18 steps x 8)
-    const bool bf16 = d.dtype == HVX_BF16;
-    if (bf16 && (!build_q || stride != 1u)) return sbail2(fail(HVX_ERR_INVARIANT, "bf16 rows are linked from their rounded f32 vectors"));
     const BuildKernels kern = pick_build_kernels(d.metric, fused, bf16);
     const WideLinkGeom wgeo = wide ? wide_link_geom(d, m, m0) : WideLinkGeom{};
     const bool link_wg_wide = wide && params->link_mode != 1u && wgeo.ok;
     const bool link_wg = !wide && params->link_mode != 1u && kern.link_wg && !kernel_w4(d.fkernel) /* 32-lane tree only */ && ncmax <= 33u && nk_rows > 0 && d.dim_main == d.dim && d.ld == d.dim &&
-                         (size_t)(ncmax + 1u) * link_ck * 8u <= 9u * 256u;
+                         (bf16 ? d.dim % 64u == 0u /* a column block never splits a 16-byte piece */ && (size_t)(ncmax + 1u) * link_ck * 4u <= (size_t)kLinkPreBf16 * 256u : (size_t)(ncmax + 1u) * link_ck * 8u <= (size_t)kLinkPre * 256u);
+    const bool one_node = one_node_batches(params);
     uint64_t done = first, batches = 0, singles = 0;
     if (!d.has_entry) { // the first node of an index: the entry point with empty rows on its layers (mutation.rs:706-739)
         d.has_entry = 1;
@@ -912,7 +676,7 @@ static int insert_range(hvx_index *ix, uint64_t first, uint64_t count, const uin
         uint32_t bsz = 1;
         const uint16_t lv0 = levels ? levels[row_at(done)] : 0;
         const bool promotes = lv0 > d.max_layer;
-        if (!promotes && !params->sequential && !bf16) { // (bf16 images: one node per step)
+        if (!promotes && !one_node) {
             uint64_t want = std::min<uint64_t>(std::max<uint64_t>(done / divisor, 1), bmax);
             want = std::min<uint64_t>(want, end - done);
             while (bsz < want && !((levels ? levels[row_at(done + bsz)] : 0) > d.max_layer)) ++bsz;
@@ -920,7 +684,7 @@ static int insert_range(hvx_index *ix, uint64_t first, uint64_t count, const uin
         const uint32_t pb = (uint32_t)(batches & 1u); // buffer set of this batch
         // (degree limits above 32 do not overlap either: at M 32 / M0 64 a batch that sees neither its own nodes nor the batch before it
         // costs 0.002 of recall@10 at ef 32 on 8 000 Gaussian rows -- 0.8216 against 0.8235 --, a fifth of the margin batching is granted)
-        const bool serial = promotes || bsz == 1u || params->sequential != 0u || params->link_mode == 1u || wide;
+        const bool serial = promotes || bsz == 1u || one_node || params->link_mode == 1u || wide;
         // the buffers of set pb were last read by the link step of batch - 2; and a serial batch (or the batch behind one) starts
         // only when everything before it is in the graph
         if (link_pending[pb] && hipStreamWaitEvent(s, ev_link[pb], 0) != hipSuccess) return sbail2(fail(HVX_ERR_DEVICE, "stream ordering failed"));
@@ -943,8 +707,14 @@ static int insert_range(hvx_index *ix, uint64_t first, uint64_t count, const uin
         a.out_status = d_status;
         a.tie_flags = ix->d_tie;
         a.build_nodes = d_iota + (done - first);
-        if (bf16) a.queries = build_q + (size_t)(done - first) * d.dim;
-        a.occupancy = (bsz > 1024u && params->link_mode != 1u) ? 2 : 1; // more nodes than SIMDs: two searches per SIMD instead of two rounds
+        if (bf16 && build_q) a.queries = build_q + (size_t)(done - first) * d.dim;
+        else if (bf16) {
+            hipLaunchKernelGGL(decode_rows_bf16_kernel, dim3((uint32_t)(((size_t)bsz * (d.dim >> 3) + 255u) / 256u)), dim3(256), 0, s, d.vecb, d_iota + (done - first), bsz, d.dim, d_bq);
+            if (hipGetLastError() != hipSuccess) return sbail2(fail(HVX_ERR_DEVICE, "launch of the bf16 query rows failed"));
+            a.queries = d_bq;
+        }
+        // more nodes than SIMDs: two searches per SIMD instead of two rounds (bf16 rows: the build search exists one per SIMD only)
+        a.occupancy = (bsz > 1024u && params->link_mode != 1u && !bf16) ? 2 : 1;
         if (launch_hnsw_wave(a, bsz, s) != hipSuccess) return sbail2(fail(HVX_ERR_DEVICE, "build search launch failed: %s", hipGetErrorString(hipGetLastError())));
         if (hipEventRecord(ev_search[pb], s) != hipSuccess || hipStreamWaitEvent(s2, ev_search[pb], 0) != hipSuccess)
             return sbail2(fail(HVX_ERR_DEVICE, "stream ordering failed"));
@@ -968,8 +738,7 @@ static int insert_range(hvx_index *ix, uint64_t first, uint64_t count, const uin
         ba.kc = kc;
         ba.selw = selw;
         // one node: its select and its links as two many-workgroup steps with every prune's distance matrix evaluated up front
-        const bool seq_step = !wide && bsz == 1u && (params->link_mode != 1u || bf16) && d.s0 + 1u <= kSeqRow && d.su + 1u <= kSeqRow;
-        if (bf16 && !seq_step && !wide) return sbail2(fail(HVX_ERR_UNSUPPORTED, "a bf16 image links rows of at most %u ids", kSeqRow - 1u));
+        const bool seq_step = !wide && bsz == 1u && params->link_mode != 1u && d.s0 + 1u <= kSeqRow && d.su + 1u <= kSeqRow;
         hipError_t e;
         if (wide) { // two ids per lane: the one-wavefront kernels for one node (f32 and bf16 rows), one workgroup per link for a batch
             e = launch_build_select_wide(ba, fused, bf16, dim3(bsz, layers), s2);
@@ -979,7 +748,7 @@ static int insert_range(hvx_index *ix, uint64_t first, uint64_t count, const uin
                 // (>= 1 024: four wavefronts per CU) that kernel is the faster link step -- 1M x 768, batches of 2 048: 13.9 s against 15.9 s --,
                 // below that the workgroup kernel is (8 000 x 128, batches <= 250: 0.22 s against 0.99 s).
                 constexpr uint32_t kWideWgMaxBatch = 1024;
-                if (bsz > 1u && bsz < kWideWgMaxBatch && link_wg_wide) {
+                if (bsz > 1u && bsz < kWideWgMaxBatch && link_wg_wide) { // (f32 rows: wide_link_geom; a bf16 batch of any size takes the one-wavefront kernel)
                     ba.ldp = wgeo.ldp;
                     ba.ncmax = wgeo.ncmax;
                     ba.link_ck = wgeo.link_ck;
@@ -1052,8 +821,17 @@ extern "C" int hvx_index_build(const hvx_index_desc *desc, const uint64_t *node_
     const uint32_t m = desc->m ? desc->m : 16u;
     const uint32_t m0 = std::max(desc->m0 ? desc->m0 : 2u * m, 2u * m); // MutationDegreeLimits (mutation.rs:178-196)
     const uint32_t efc = params->ef_construction ? params->ef_construction : 200u;
-    if (desc->dtype != HVX_F32) return fail(HVX_ERR_UNSUPPORTED, "the device build reads f32 rows (import the built graph with a reduced-precision dtype afterwards)");
+    if (desc->dtype != HVX_F32 && desc->dtype != HVX_BF16)
+        return fail(HVX_ERR_UNSUPPORTED, "the device build reads f32 and bf16 rows (import the built graph with dtype fp8 afterwards)");
     if (m0 > 64u || m > 32u) return fail(HVX_ERR_UNSUPPORTED, "device build serves m0 <= 64 (m <= 32)");
+    if (desc->dtype == HVX_BF16) { // what the bf16 import and the unrolled build search over bf16 rows serve
+        const uint32_t nk = desc->dim >> 5;
+        const bool dim_ok = desc->dim % 32u == 0u && (nk == 4 || nk == 8 || nk == 12 || nk == 16 || nk == 24 || nk == 32 || nk == 48);
+        if (!dim_ok || desc->float_kernel != HVX_KERNEL_AVX_FMA || (desc->metric != HVX_L2_SQUARED && desc->metric != HVX_COSINE_HALF))
+            return fail(HVX_ERR_UNSUPPORTED, "the device build over bf16 rows serves L2 / cosine, the AVX+FMA summation tree and dim in {128, 256, 384, 512, 768, 1024, 1536}");
+        if (wave_build_need(std::max(efc, m0), std::max(efc, 2u * m)) > kBeamNarrowMax)
+            return fail(HVX_ERR_UNSUPPORTED, "the device build over bf16 rows serves max(ef_construction, m0, 2 m) <= %u", kBeamNarrowMax - kBeamSlack);
+    }
     if (wave_build_need(std::max(efc, m0), std::max(efc, 2u * m)) > kBeamMax) return fail(HVX_ERR_UNSUPPORTED, "device build serves ef_construction <= 800");
     const uint32_t ef0 = std::max(efc, m0);
 
@@ -1085,7 +863,7 @@ extern "C" int hvx_index_build(const hvx_index_desc *desc, const uint64_t *node_
     // neighbours into one batch, where they cannot see each other: insert in the order (i * stride) mod n instead, stride ~ 0.618 n and
     // coprime with n (position 0 stays row 0).  Sequential mode keeps id order: it IS the reference's order.
     uint32_t stride = 1;
-    if (params->scatter && !params->sequential && n > 2) {
+    if (params->scatter && !one_node_batches(params) && n > 2) {
         auto gcd = [](uint64_t a, uint64_t b) { while (b) { const uint64_t t = a % b; a = b; b = t; } return a; };
         uint64_t st = (uint64_t)((double)n * 0.6180339887498949);
         while (st > 1 && gcd(st, n) != 1) --st;
@@ -1121,7 +899,12 @@ extern "C" int hvx_index_insert_batch(hvx_index *ix, const uint64_t *node_ids, c
     HIP_TRY(hipSetDevice(ix->device));
     DevIndex &d = ix->dev;
     if (d.dtype != HVX_F32 && d.dtype != HVX_BF16) return fail(HVX_ERR_UNSUPPORTED, "rows are inserted into f32 and bf16 images (fp8 images are read-only)");
-    const bool bf16 = d.dtype == HVX_BF16; // (round 6: rounded, validated, packed, linked one node at a time over the bf16 rows)
+    const bool bf16 = d.dtype == HVX_BF16; // (rounded, validated, packed, linked over the bf16 rows)
+    hvx_build_params one = *params;
+    if (bf16 && params->sequential == HVX_BUILD_AUTO) { // the library's choice for appends to a bf16 image: one node per step
+        one.sequential = HVX_BUILD_ONE_NODE;
+        params = &one;
+    }
     const uint32_t m = ix->desc.m ? ix->desc.m : 16u;
     const uint32_t m0 = std::max(ix->desc.m0 ? ix->desc.m0 : 2u * m, 2u * m);
     const uint32_t efc = params->ef_construction ? params->ef_construction : 200u;
@@ -1349,7 +1132,8 @@ extern "C" int hvx_index_link_rows(hvx_index *ix, const uint64_t *from_ids, cons
     const uint32_t m = ix->desc.m ? ix->desc.m : 16u;
     const uint32_t m0 = std::max(ix->desc.m0 ? ix->desc.m0 : 2u * m, 2u * m);
     const bool fused = kernel_fused(d.fkernel);
-    const BuildKernels kern = pick_build_kernels(d.metric, fused);
+    const bool bf16 = d.dtype == HVX_BF16;
+    const BuildKernels kern = pick_build_kernels(d.metric, fused, bf16);
     const uint32_t ncmax = std::max(m0, m) + 1u;
     const uint32_t nk_rows = d.dim_main >> 5;
     const uint32_t link_ck = std::min<uint32_t>(8u, (nk_rows + 1u) & ~1u);
@@ -1357,11 +1141,15 @@ extern "C" int hvx_index_link_rows(hvx_index *ix, const uint64_t *from_ids, cons
     const bool wide = std::max(m0, m) > 32u;
     const WideLinkGeom wgeo = wide ? wide_link_geom(d, m, m0) : WideLinkGeom{};
     const uint32_t selw = wide ? kSelWide : 32u;
-    if (std::max(m0, m) > 64u || (wide && (!wgeo.ok || d.s0 < m0)))
-        return fail(HVX_ERR_UNSUPPORTED, "the link workgroups serve f32 rows, L2 / cosine, dim %% 32 == 0, m0 <= 64 (row stride >= m0, <= 64)");
-    if (!wide && (d.dtype != HVX_F32 || !kern.link_wg || kernel_w4(d.fkernel) || ncmax > 33u || nk_rows == 0 || d.dim_main != d.dim || d.ld != d.dim || d.s0 < m0 ||
-        (size_t)(ncmax + 1u) * link_ck * 8u > 9u * 256u))
-        return fail(HVX_ERR_UNSUPPORTED, "the link workgroups serve f32 rows, L2 / cosine, dim %% 32 == 0, m0 <= 64 (row stride >= m0, <= 64)");
+    // one refusal per cause
+    if (d.dtype != HVX_F32 && !bf16) return fail(HVX_ERR_UNSUPPORTED, "the link workgroups serve f32 and bf16 rows (this image holds dtype %u)", d.dtype);
+    if (std::max(m0, m) > 64u) return fail(HVX_ERR_UNSUPPORTED, "the link workgroups serve m0 <= 64 (m <= 32)");
+    if (wide && bf16) return fail(HVX_ERR_UNSUPPORTED, "the link workgroups serve bf16 rows with m0 <= 32 (the workgroup kernel for m0 <= 64 reads f32 rows)");
+    if (bf16 && d.dim % 64u != 0u) return fail(HVX_ERR_UNSUPPORTED, "the link workgroups serve bf16 rows with dim %% 64 == 0");
+    if (d.s0 < m0) return fail(HVX_ERR_UNSUPPORTED, "the image's layer-0 rows (%u ids) are narrower than m0 = %u", d.s0, m0);
+    const bool fits = bf16 ? (size_t)(ncmax + 1u) * link_ck * 4u <= (size_t)kLinkPreBf16 * 256u : (size_t)(ncmax + 1u) * link_ck * 8u <= (size_t)kLinkPre * 256u;
+    if (wide ? !wgeo.ok : (!kern.link_wg || kernel_w4(d.fkernel) || ncmax > 33u || nk_rows == 0 || d.dim_main != d.dim || d.ld != d.dim || !fits))
+        return fail(HVX_ERR_UNSUPPORTED, "the link workgroups serve L2 / cosine under the 256-bit summation trees, dim %% 32 == 0, rows of at most 64 ids");
     std::vector<uint32_t> h_nodes(n_links), h_sel((size_t)n_links * selw, kSentinel), h_cnt(n_links, 1u);
     for (uint32_t i = 0; i < n_links; ++i) {
         const uint32_t f = ix->find(from_ids[i]), t = ix->find(to_ids[i]);

@@ -103,6 +103,10 @@ __device__ __forceinline__ void remove_edge_w(const BuildArgs &a, uint32_t layer
     unlock_row_w(a.locks, owner, lane);
 }
 
+using BuildKernel = void (*)(BuildArgs);
+// build_link_wg_kernel over bf16 rows (hvx_build_bf16.hip; hvx_build_link_wg.h), L2 / cosine
+BuildKernel build_link_wg_bf16_kernel(uint32_t metric);
+
 // ---- degree limits above 32 (hvx_build_wide.hip): Mmax = max(m0, m) <= 64 ----
 constexpr uint32_t kCandWide = 128; // candidates kept per layer and node (2 * Mmax <= 128)
 constexpr uint32_t kSelWide = 64;   // selected neighbours per layer and node

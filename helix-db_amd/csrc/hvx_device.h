@@ -64,6 +64,25 @@ __host__ __device__ __forceinline__ uint32_t bf16_slot_of(uint32_t i) {
     const uint32_t k = i >> 5, s = (i >> 2) & 7u, e = i & 3u;
     return (k >> 1) * 64u + s * 8u + (k & 1u) * 4u + e;
 }
+// A COLUMN BLOCK of ck chunks (ck even: a block never splits a piece) of several bf16 rows, staged as plain-order f32 (the batched link
+// step, hvx_build.hip: build_link_wg_kernel).  The block is cut into 16-byte pieces, w = ck * 4 per row: piece e belongs to row e / w,
+// is piece blk * w + col of that row in HBM (col = e % w = 8 * chunk pair + slot), and its eight values widen into the float4 at
+// floats dst (chunk 2 * pair) and dst + 32 (chunk 2 * pair + 1) of the row's block.  Eight consecutive pieces are 128 contiguous bytes
+// in HBM and two runs of 128 contiguous bytes in LDS.
+struct Bf16BlockPiece { uint32_t row, col, src, dst; };
+// piece t = 8 * chunk pair + slot of a row (or of a row's column block) -> first float of its chunk 2 * pair in plain order
+__host__ __device__ __forceinline__ uint32_t bf16_piece_dst(uint32_t t) { return (t >> 3) * 64u + (t & 7u) * 4u; }
+__host__ __device__ __forceinline__ Bf16BlockPiece bf16_block_piece(uint32_t e, uint32_t blk, uint32_t ck) {
+    const uint32_t w = ck * 4u, r = e / w, c = e - r * w;
+    return Bf16BlockPiece{r, c, blk * w + c, bf16_piece_dst(c)};
+}
+// the eight bf16 values of a piece (four 32-bit words), widened: exact
+__host__ __device__ __forceinline__ void bf16_piece_widen(const uint32_t w[4], float lo[4], float hi[4]) {
+    lo[0] = __builtin_bit_cast(float, w[0] << 16); lo[1] = __builtin_bit_cast(float, w[0] & 0xFFFF0000u);
+    lo[2] = __builtin_bit_cast(float, w[1] << 16); lo[3] = __builtin_bit_cast(float, w[1] & 0xFFFF0000u);
+    hi[0] = __builtin_bit_cast(float, w[2] << 16); hi[1] = __builtin_bit_cast(float, w[2] & 0xFFFF0000u);
+    hi[2] = __builtin_bit_cast(float, w[3] << 16); hi[3] = __builtin_bit_cast(float, w[3] & 0xFFFF0000u);
+}
 // fp8 device layout (dim % 128 == 0): element i = 32*chunk + 4*slot + e is stored at
 // 128*(chunk/4) + 16*slot + 4*(chunk%4) + e: a lane's 16 bytes hold its four virtual lanes of FOUR chunks.
 __host__ __device__ __forceinline__ uint32_t fp8_slot_of(uint32_t i) {

@@ -34,16 +34,36 @@ __device__ __forceinline__ BuildLds carve_build(char *smem, uint32_t ld) {
 }
 static size_t build_lds_bytes(uint32_t ld) { return (((size_t)ld * 4u + 15u) & ~(size_t)15u) + 4 * 256; }
 
-__device__ __forceinline__ void stage_row(const DevIndex &ix, float *qv, uint32_t node, int lane) {
+// (BF: a bf16 row, widened piece by piece into plain order -- exact)
+template <bool BF = false> __device__ __forceinline__ void stage_row(const DevIndex &ix, float *qv, uint32_t node, int lane) {
     __syncthreads();
-    const float *r = ix.vec + (size_t)node * ix.ld;
-    for (uint32_t t = (uint32_t)lane; t < ix.ld; t += 64) qv[t] = r[t];
+    if constexpr (BF) {
+        const uint4 *r = reinterpret_cast<const uint4 *>(ix.vecb + (size_t)node * ix.dim);
+        for (uint32_t t = (uint32_t)lane; t < ix.dim >> 3; t += 64) {
+            const uint4 x = r[t];
+            const uint32_t w[4] = {x.x, x.y, x.z, x.w};
+            float lo[4], hi[4];
+            bf16_piece_widen(w, lo, hi);
+            float *dst = qv + bf16_piece_dst(t);
+            *reinterpret_cast<float4 *>(dst) = make_float4(lo[0], lo[1], lo[2], lo[3]);
+            *reinterpret_cast<float4 *>(dst + 32) = make_float4(hi[0], hi[1], hi[2], hi[3]);
+        }
+    } else {
+        const float *r = ix.vec + (size_t)node * ix.ld;
+        for (uint32_t t = (uint32_t)lane; t < ix.ld; t += 64) qv[t] = r[t];
+    }
     __syncthreads();
+}
+// one resident row against the staged one, one 8-lane group, reference summation order
+template <uint32_t METRIC, bool FUSED, bool BF>
+__device__ __forceinline__ float staged_distance(const DevIndex &ix, const float *qv, float qhdr, uint32_t node, int j) {
+    if constexpr (BF) return group_distance_bf16<METRIC>(ix, qv, qhdr, node, j);
+    else return group_distance<METRIC, FUSED>(ix, qv, qhdr, node, j);
 }
 
 // mod.rs:809-856 select_diverse over L.cid/L.csc[0..hyd) (sorted closest first, all hydrated), at most m kept, then the
 // backfill with the closest remaining candidates (:845-854).  L.kept[0..ns) = the selection in selection order.
-template <uint32_t METRIC, bool FUSED>
+template <uint32_t METRIC, bool FUSED, bool BF = false>
 __device__ __forceinline__ uint32_t select_diverse_dev(const DevIndex &ix, const BuildLds &L, uint32_t hyd, uint32_t m, int lane) {
     const int grp = lane >> 3, j = lane & 7;
     uint32_t ns = 0;
@@ -52,12 +72,12 @@ __device__ __forceinline__ uint32_t select_diverse_dev(const DevIndex &ix, const
         const float si = L.csc[i];
         bool diverse = true;
         if (ns) {
-            stage_row(ix, L.qv, ci, lane);
+            stage_row<BF>(ix, L.qv, ci, lane);
             const float chdr = ix.hdr[ci];
             for (uint32_t p0 = 0; p0 < ns; p0 += 8) {
                 const uint32_t g = p0 + (uint32_t)grp;
                 const uint32_t other = L.kept[g < ns ? g : ns - 1u];
-                const float pd = group_distance<METRIC, FUSED>(ix, L.qv, chdr, other, j);
+                const float pd = staged_distance<METRIC, FUSED, BF>(ix, L.qv, chdr, other, j);
                 if (__ballot(g < ns && pd < si)) { diverse = false; break; } // strict < rejects (mod.rs:832)
             }
         }
@@ -100,11 +120,11 @@ __device__ __forceinline__ void store_canonical(uint32_t *row, uint32_t stride, 
 // `maxn` by select_diverse + backfill with the owner as the reference point: the prune of add_bidirectional_link (mutation.rs:1545-1575) and of
 // relink_neighbor (mutation.rs:1959-1984, 2012-2040).  Returns the number kept; L.kept[0..kept) holds them in selection order.
 // *bad is set when a distance is not a valid score (Candidate::try_new fails: the reference aborts the mutation).
-template <uint32_t METRIC, bool FUSED>
+template <uint32_t METRIC, bool FUSED, bool BF = false>
 __device__ __forceinline__ uint32_t prune_row_dev(const DevIndex &ix, const BuildLds &L, uint32_t owner, uint32_t v, uint32_t nc, uint32_t maxn, int lane,
                                                   bool *bad) {
     const int grp = lane >> 3, j = lane & 7;
-    stage_row(ix, L.qv, owner, lane);
+    stage_row<BF>(ix, L.qv, owner, lane);
     const float ohdr = ix.hdr[owner];
     __syncthreads();
     if ((uint32_t)lane < nc) L.kept[lane] = v; // scratch: unsorted candidate ids
@@ -112,7 +132,7 @@ __device__ __forceinline__ uint32_t prune_row_dev(const DevIndex &ix, const Buil
     for (uint32_t p0 = 0; p0 < nc; p0 += 8) {
         const uint32_t g = p0 + (uint32_t)grp;
         const uint32_t other = L.kept[g < nc ? g : nc - 1u];
-        const float d = group_distance<METRIC, FUSED>(ix, L.qv, ohdr, other, j);
+        const float d = staged_distance<METRIC, FUSED, BF>(ix, L.qv, ohdr, other, j);
         if (g < nc && j == 0) L.dtmp[g] = d;
     }
     __syncthreads();
@@ -128,7 +148,7 @@ __device__ __forceinline__ uint32_t prune_row_dev(const DevIndex &ix, const Buil
     __syncthreads();
     if ((uint32_t)lane < nc) { L.cid[rank] = v; L.csc[rank] = dmine; }
     __syncthreads();
-    return select_diverse_dev<METRIC, FUSED>(ix, L, nc, maxn, lane);
+    return select_diverse_dev<METRIC, FUSED, BF>(ix, L, nc, maxn, lane);
 }
 
 

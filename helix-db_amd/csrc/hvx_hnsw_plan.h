@@ -75,7 +75,7 @@ inline bool wave_generic_serves(const DevIndex &ix, uint32_t need) {
 }
 inline bool hnsw_wave_adaptive_supported(const HnswArgs &a) { return hnsw_wave_supported(a) || wave_generic_serves(a.ix, a.ef + kBeamSlack); }
 // the searches of a device build / insert: the beam holds max(ef_construction, 2 M) entries on every layer.  The unrolled builds
-// serve L2 / cosine, the AVX+FMA tree, dim in {128,...,1536}, beams up to 352 + 32 (f32 rows; bf16 rows for one-node inserts);
+// serve L2 / cosine, the AVX+FMA tree, dim in {128,...,1536}, beams up to 352 + 32 (f32 rows; bf16 rows, one search per SIMD: builds, inserts, upserts);
 // everything else over f32 rows (any dimension, Manhattan, the scalar / AVX summation trees, beams up to 800 + 32) takes the GENERIC
 // build of the same kernel
 inline uint32_t wave_build_need(uint32_t ef_layer0, uint32_t ef_upper) { return std::max(ef_layer0, ef_upper) + kBeamSlack; }

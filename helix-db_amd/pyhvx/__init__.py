@@ -107,6 +107,19 @@ def decode_index_metadata(value: bytes) -> dict:
     return out
 
 
+BUILD_AUTO, BUILD_ONE_NODE, BUILD_BATCHED = 0, 1, 2  # enum hvx_build_batching (hvx_build_params.sequential)
+
+
+def _batching(sequential):
+    """hvx_build_params.sequential from a bool (True: one node per batch, False: the library's choice) or a BUILD_* value."""
+    if isinstance(sequential, (bool, np.bool_)):
+        return BUILD_ONE_NODE if sequential else BUILD_AUTO
+    v = int(sequential)
+    if v not in (BUILD_AUTO, BUILD_ONE_NODE, BUILD_BATCHED):
+        raise ValueError(f"sequential is a bool or one of BUILD_AUTO / BUILD_ONE_NODE / BUILD_BATCHED, not {sequential!r}")
+    return v
+
+
 class BuildParams(C.Structure):  # hvx_build_params
     _fields_ = [("ef_construction", C.c_uint32), ("max_batch", C.c_uint32), ("batch_divisor", C.c_uint32), ("sequential", C.c_uint32),
                 ("link_mode", C.c_uint32), ("scatter", C.c_uint32), ("reserve_rows", C.c_uint64), ("reserve_upper_rows", C.c_uint64)]
@@ -586,22 +599,24 @@ class ValidatedVectorReadIndex:
     @classmethod
     def build(cls, *, dim, metric, node_ids, vectors, levels=None, m=16, m0=32, ef_construction=200, max_batch=2048,
               batch_divisor=32, sequential=False, device=-1, search_max_batch=None, float_kernel=KERNEL_AVX_FMA, link_mode=0, scatter=False,
-              reserve_rows=0, reserve_upper_rows=None):
+              reserve_rows=0, reserve_upper_rows=None, dtype=F32):
         """GPU-assisted HNSW build (hvx_index_build): the reference's insert_hnsw for batches of nodes on the device.
         Returns (index, stats dict).  `vectors` may be a host array or a torch tensor resident on the device.
-        Degree limits m0 <= 64 (m <= 32: the reference's scale configuration M 32 / M0 64 included); above: ERR_UNSUPPORTED."""
+        Degree limits m0 <= 64 (m <= 32: the reference's scale configuration M 32 / M0 64 included); above: ERR_UNSUPPORTED.
+        dtype=BF16 builds the image in bf16 (the graph of the ROUNDED vectors; L2 / cosine, dim in {128, ..., 1536},
+        max(ef_construction, m0, 2 m) <= 352); `sequential` is a bool or a BUILD_* value."""
         ids = np.ascontiguousarray(node_ids, dtype=np.uint64)
         dev_rows = hasattr(vectors, "data_ptr")
         if dev_rows:
             _sync_producer(vectors)
         vec = None if dev_rows else (np.ascontiguousarray(vectors, dtype=np.float32).reshape(ids.size, dim) if ids.size else np.zeros((0, dim), np.float32))
         lv = None if levels is None else np.ascontiguousarray(levels, dtype=np.uint16)
-        d = _Desc(dim=dim, metric=metric, dtype=F32, float_kernel=float_kernel, n=ids.size, m=m, m0=m0, has_entry=0, max_layer=0,
+        d = _Desc(dim=dim, metric=metric, dtype=dtype, float_kernel=float_kernel, n=ids.size, m=m, m0=m0, has_entry=0, max_layer=0,
                   entry_point=0, shard_id_lo=int(ids[0]) if ids.size else 0, shard_id_hi=int(ids[-1]) if ids.size else 0,
                   device=device, max_batch=max(max_batch, search_max_batch or 1024))
         if reserve_upper_rows is None:  # the expected number of upper rows of `reserve_rows` nodes under the layer rule, with slack
             reserve_upper_rows = int(reserve_rows / max(m - 1, 1) * 1.5) + (64 if reserve_rows else 0)
-        bp = BuildParams(ef_construction=ef_construction, max_batch=max_batch, batch_divisor=batch_divisor, sequential=1 if sequential else 0,
+        bp = BuildParams(ef_construction=ef_construction, max_batch=max_batch, batch_divisor=batch_divisor, sequential=_batching(sequential),
                          link_mode=link_mode, scatter=1 if scatter else 0, reserve_rows=int(reserve_rows), reserve_upper_rows=int(reserve_upper_rows))
         st = BuildStats()
         h = _vp()
@@ -612,14 +627,15 @@ class ValidatedVectorReadIndex:
     def insert_batch(self, node_ids, vectors, levels=None, *, ef_construction=200, max_batch=2048, batch_divisor=32, sequential=False, link_mode=0):
         """hvx_index_insert_batch: append rows to a growable image (build(..., reserve_rows=...)) and link them into the graph; the new
         generation is visible on this handle when the call returns (forks: refresh()).  Returns the build-stats dict of the batch.
-        f32 and bf16 images with degree limits m0 <= 64 (m <= 32); above: ERR_UNSUPPORTED with nothing changed."""
+        f32 and bf16 images with degree limits m0 <= 64 (m <= 32); above: ERR_UNSUPPORTED with nothing changed.
+        A bf16 image links one node per step unless sequential=BUILD_BATCHED asks for batches as the build runs them."""
         ids = np.ascontiguousarray(node_ids, dtype=np.uint64)
         dev_rows = hasattr(vectors, "data_ptr")
         if dev_rows:
             _sync_producer(vectors)
         vec = None if dev_rows else np.ascontiguousarray(vectors, dtype=np.float32).reshape(ids.size, self.dim)
         lv = None if levels is None else np.ascontiguousarray(levels, dtype=np.uint16)
-        bp = BuildParams(ef_construction=ef_construction, max_batch=max_batch, batch_divisor=batch_divisor, sequential=1 if sequential else 0,
+        bp = BuildParams(ef_construction=ef_construction, max_batch=max_batch, batch_divisor=batch_divisor, sequential=_batching(sequential),
                          link_mode=link_mode)
         st = BuildStats()
         L = lib()

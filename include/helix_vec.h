@@ -662,7 +662,7 @@ int hvx_hydrator_finish_reserve(const hvx_hydrator *, const hvx_index_desc *tmpl
  * mod.rs:809-856, add_bidirectional_link with prune + reverse-edge removal :1498-1583,1890-1908) over rows resident in HBM,
  * for batches of consecutive nodes.  `levels[i]` = the node's top layer (drawn by the host with select_layer_from_uniform,
  * mod.rs:776-796 -- the reference's draw is intentionally non-deterministic, randomness.rs:41-46).  Nodes are inserted in
- * node-id order.  With params->sequential != 0 every batch holds ONE node and the graph equals the reference's sequential
+ * node-id order.  With params->sequential = HVX_BUILD_ONE_NODE every batch holds ONE node and the graph equals the reference's sequential
  * insertion row for row; otherwise a batch holds up to min(max_batch, inserted / batch_divisor) nodes that do not see each
  * other (a node above the current top layer is always inserted alone and becomes the entry point).  The result is an
  * ordinary searchable hvx_index; hvx_index_export_graph hands the rows back for the host to persist (values/vectors.rs).
@@ -672,12 +672,25 @@ int hvx_hydrator_finish_reserve(const hvx_hydrator *, const hvx_index_desc *tmpl
  * desc->max_batch bounds the batch size.  Degree limits above 32 take the kernels of csrc/hvx_build_wide.hip (two ids per lane, 128-bit
  * masks): same rows as the reference's insertion in sequential mode, same invariants in batches.  Larger limits: HVX_ERR_UNSUPPORTED
  * before anything is allocated.
+ * desc->dtype = HVX_BF16 builds the image in bf16: the rows are rounded, validated and packed as hvx_index_import does, and the SAME loop
+ * then runs over the packed rows -- every distance is the reference's on the ROUNDED vectors, sequential mode equals the reference's
+ * insertion of the rounded vectors row for row, the default runs batches exactly as over f32 rows (the link step widens bf16 column
+ * blocks into LDS: half the bytes of an f32 build).  Served: what the bf16 import and the unrolled build search serve -- cosine /
+ * Euclidean, the AVX+FMA tree, dim in {128,256,384,512,768,1024,1536}, max(ef_construction, m0, 2 m) <= 352, m0 <= 64 (above 32: the
+ * one-wavefront kernels of csrc/hvx_build_wide.hip link every batch); anything else, and HVX_FP8_E4M3: HVX_ERR_UNSUPPORTED before
+ * anything is allocated.  Peak memory is the f32 staging copy plus the bf16 rows until packing ends.
  */
+enum hvx_build_batching {    /* hvx_build_params.sequential */
+    HVX_BUILD_AUTO = 0,      /* the library's choice: batches, except hvx_index_insert_batch into a bf16 image (one node per step) */
+    HVX_BUILD_ONE_NODE = 1,  /* one node per batch: the reference's insertion order exactly */
+    HVX_BUILD_BATCHED = 2    /* batches on every image (on f32 images the same as HVX_BUILD_AUTO) */
+};
 typedef struct hvx_build_params {
     uint32_t ef_construction; /* 0 => 200 (mod.rs:702-708) */
     uint32_t max_batch;       /* 0 => 2048 */
     uint32_t batch_divisor;   /* 0 => 32: batch <= nodes already inserted / divisor (degree limits above 32: / (2 * divisor)) */
-    uint32_t sequential;      /* 1 => one node per batch: the reference's insertion order exactly */
+    uint32_t sequential;      /* enum hvx_build_batching: 0 => the library's choice, 1 => one node per batch (the reference's insertion
+                                 order exactly), 2 => batches on every image */
     uint32_t link_mode;       /* batched link step: 0 => one workgroup per link with the prune evaluated from LDS whenever the rows fit
                                  (Mmax + 2 rows of ld floats <= 160 KB), 1 => one wavefront per node (links one after the other).
                                  One node at a time (sequential = 1, upserts, promotions): 0 => its select and its links as two many-workgroup
@@ -700,7 +713,8 @@ int hvx_index_build(const hvx_index_desc *desc, const uint64_t *node_ids, const 
  * Incremental insert into a LIVE image (VectorIndex::insert -> insert_hnsw, mutation.rs:642-895): `count` new nodes -- ids ascending
  * and above every id of the image, f32 vectors (host or device memory), levels as hvx_index_build takes them -- are appended to
  * the spare capacity of an image built with hvx_build_params.reserve_rows or hydrated with hvx_index_import_reserve
- * (HVX_ERR_CANDIDATE_LIMIT when they do not fit; bf16 images: the vectors are rounded first and linked one node at a time), degree
+ * (HVX_ERR_CANDIDATE_LIMIT when they do not fit; bf16 images: the vectors are rounded first and, unless params->sequential =
+ * HVX_BUILD_BATCHED asks for batches as hvx_index_build runs them, linked one node at a time), degree
  * limits m0 <= 64 / m <= 32 on rows of at most 64 ids as hvx_index_build serves them (above: HVX_ERR_UNSUPPORTED, nothing changed),
  * validated like imported rows (an invalid vector fails the call before anything changes), given headers and -- when SimHash
  * rows are attached -- SimHash rows, and linked into the graph by the loop hvx_index_build runs: params->sequential = 1 is the
@@ -766,8 +780,8 @@ uint64_t hvx_index_row_capacity(const hvx_index *); /* rows the image can hold *
  * BATCHED build links with (one workgroup per link -- 256 threads for m0 <= 32, 1 024 for m0 <= 64 --, the prune evaluated eagerly from LDS): the links are applied one
  * launch after the other in list order (concurrent = 0: a defined order, what the parity tests compare with the oracle's
  * select_diverse) or all in ONE launch (concurrent = 1: the batched build's situation -- rows change under their locks in an
- * undefined order).  Served shapes = the workgroup kernel's: f32 rows, L2 / cosine, dim % 32 == 0, m0 <= 64 (rows of at most 64 ids).  The index must
- * not be searched concurrently.
+ * undefined order).  Served shapes = the workgroup kernel's: f32 rows, L2 / cosine, dim % 32 == 0, m0 <= 64 (rows of at most 64 ids); bf16
+ * rows with m0 <= 32 (the prune is evaluated on the rounded vectors).  The index must not be searched concurrently.
  */
 int hvx_index_link_rows(hvx_index *, const uint64_t *from_ids, const uint64_t *to_ids, uint32_t n_links, uint32_t concurrent);
 /*
