@@ -23,7 +23,8 @@
 // otherwise; select / link kernels per metric and tree), m0 <= 64 (m <= 32), ef_construction <= 800.  The kernels of THIS file hold one id
 // per lane and 64-bit masks: degree limits up to 32.  Limits up to 64 (the reference's scale fixture, M 32 / M0 64) run the kernels of
 // hvx_build_wide.hip -- two ids per lane, 128-bit masks, 128 search candidates per layer and node -- picked per index in insert_range;
-// their one-node steps are the one-wavefront kernels (f32 and bf16 rows); their batches hold half the fraction and do not overlap search and link.
+// their one-node steps are the two many-workgroup kernels of hvx_build_wide_seq.hip (f32 and bf16 rows; link_mode = 1: the one-wavefront
+// kernels); their batches hold half the fraction and do not overlap search and link.
 // bf16 images (hvx_index_build with dtype bf16, inserts, upserts, hvx_index_link_rows): the same loop over the packed rows.  The build search
 // takes the batch's rows widened to f32 as its queries (decode_rows_bf16_kernel), the BF builds of the select / link kernels widen bf16 rows
 // on their way into LDS (stage_row<BF>; build_link_wg_kernel<.., BF> in hvx_build_link_wg.h, instantiated in hvx_build_bf16.hip), the one-node
@@ -518,6 +519,8 @@ static BuildKernels pick_build_kernels(uint32_t metric, bool fused, bool bf16 = 
 // hvx_build_params.sequential: HVX_BUILD_ONE_NODE (and any value the header does not name) = one node per batch
 static bool one_node_batches(const hvx_build_params *p) { return p->sequential != HVX_BUILD_AUTO && p->sequential != HVX_BUILD_BATCHED; }
 
+extern "C" uint32_t hvx_index_last_write_path(const hvx_index *ix) { return ix ? ix->last_write_path : 0u; }
+
 extern "C" void hvx_build_params_default(hvx_build_params *p) {
     if (!p) return;
     memset(p, 0, sizeof(*p));
@@ -587,12 +590,16 @@ static int insert_range(hvx_index *ix, uint64_t first, uint64_t count, const uin
     const bool wide = std::max(m0, m) > 32u;
     const uint32_t kc = wide ? kCandWide : kCand, selw = wide ? kSelWide : 32u;
     const bool bf16 = d.dtype == HVX_BF16;
+    // ... whose one-node batches take the many-workgroup steps of hvx_build_wide_seq.hip wherever their geometry fits (rows <= 64 ids: above)
+    const bool wide_seq = wide && params->link_mode != 1u && wide_seq_geom(m, m0, layers_max).ok;
     const size_t sz_cids = (size_t)layers_max * bmax * kc, sz_cnt = (size_t)layers_max * bmax, sz_sel = (size_t)layers_max * bmax * selw;
     int rc;
     {
         auto up = [](size_t b) { return (b + 255u) & ~(size_t)255u; };
         const size_t b_iota = up(count * 4), b_cids = up(2 * sz_cids * 8), b_csc = up(2 * sz_cids * 4), b_cnt = up(2 * sz_cnt * 4), b_sel = up(2 * sz_sel * 4),
-                     b_status = up((size_t)bmax * 4), b_err = 256, b_tick = up(2 * 64 * 4), b_gdm = up((size_t)layers_max * kSeqLayerDm * 4),
+                     b_status = up((size_t)bmax * 4), b_err = 256, b_tick = up(2 * 64 * 4),
+                     // the one-node steps' matrices: wide images by their geometry (a 129 x 128 select matrix and 64 link matrices on layer 0)
+                     b_gdm = up((wide_seq ? wide_seq_geom(m, m0, layers_max).total_floats() : (size_t)layers_max * kSeqLayerDm) * 4),
                      b_bq = (bf16 && !build_q) ? up((size_t)bmax * d.dim * 4) : 0;
         const size_t need = b_iota + b_cids + b_csc + 2 * b_cnt + b_sel + b_status + b_err + b_tick + b_gdm + b_bq;
         if (need > ix->ins_cap) {
@@ -740,7 +747,14 @@ static int insert_range(hvx_index *ix, uint64_t first, uint64_t count, const uin
         // one node: its select and its links as two many-workgroup steps with every prune's distance matrix evaluated up front
         const bool seq_step = !wide && bsz == 1u && params->link_mode != 1u && d.s0 + 1u <= kSeqRow && d.su + 1u <= kSeqRow;
         hipError_t e;
-        if (wide) { // two ids per lane: the one-wavefront kernels for one node (f32 and bf16 rows), one workgroup per link for a batch
+        uint32_t path = wide ? HVX_WRITE_WIDE : 0u; // hvx_index_last_write_path
+        if (wide && bsz == 1u && wide_seq) { // two ids per lane, one node: select and links as two many-workgroup steps (f32 and bf16 rows)
+            ba.gdm = d_gdm;
+            ba.tick = d_tick;
+            e = launch_build_select_wide_seq(ba, fused, bf16, s2);
+            if (e == hipSuccess) e = launch_build_link_wide_seq(ba, fused, bf16, s2);
+            path |= HVX_WRITE_EAGER_STEPS;
+        } else if (wide) { // the one-wavefront kernels for one node (link_mode = 1), one workgroup per link for a batch
             e = launch_build_select_wide(ba, fused, bf16, dim3(bsz, layers), s2);
             if (e == hipSuccess) {
                 // The workgroup kernel reads 2 145 pairs x dim out of LDS per link: LDS-bandwidth bound, ~48 us per link at dim 768 with one
@@ -753,8 +767,10 @@ static int insert_range(hvx_index *ix, uint64_t first, uint64_t count, const uin
                     ba.ncmax = wgeo.ncmax;
                     ba.link_ck = wgeo.link_ck;
                     e = launch_build_link_wide_wg(ba, fused, layers, wgeo.lds, s2);
+                    path |= HVX_WRITE_LINK_WG;
                 } else {
                     e = launch_build_link_wide(ba, fused, bf16, bsz, s2);
+                    path |= HVX_WRITE_ONE_WAVE;
                 }
             }
         } else if (seq_step) {
@@ -765,6 +781,7 @@ static int insert_range(hvx_index *ix, uint64_t first, uint64_t count, const uin
             ba.g0 = 96u; ba.gu = 12u; // 128 row groups per workgroup: <= 32 links x 561 pairs on layer 0, <= 16 x 153 above
             hipLaunchKernelGGL(kern.link_seq, dim3(ba.g0 + (layers - 1u) * ba.gu), dim3(1024), seq_lds_bytes(), s2, ba);
             e = hipGetLastError();
+            path |= HVX_WRITE_EAGER_STEPS;
         } else {
             e = launch_build(kern.select, dim3(bsz, layers), ba, s2);
         }
@@ -774,10 +791,13 @@ static int insert_range(hvx_index *ix, uint64_t first, uint64_t count, const uin
                 ba.ncmax = ncmax;
                 ba.link_ck = link_ck;
                 e = launch_link_wg(kern.link_wg, ba, layers, link_lds, s2);
+                path |= HVX_WRITE_LINK_WG;
             } else { // one node (the reference's order exactly), or rows the workgroup kernel does not serve: one wavefront per node
                 e = launch_build(kern.link, dim3(bsz), ba, s2);
+                path |= HVX_WRITE_ONE_WAVE;
             }
         }
+        ix->last_write_path |= path;
         if (e != hipSuccess) return sbail2(fail(HVX_ERR_DEVICE, "build launch failed: %s", hipGetErrorString(e)));
         if (hipEventRecord(ev_link[pb], s2) != hipSuccess) return sbail2(fail(HVX_ERR_DEVICE, "stream ordering failed"));
         link_pending[pb] = true;
@@ -893,9 +913,10 @@ extern "C" int hvx_index_insert_batch(hvx_index *ix, const uint64_t *node_ids, c
     hvx_build_params_default(&dflt);
     if (!params) params = &dflt;
     if (stats) memset(stats, 0, sizeof(*stats));
-    if (count == 0) return HVX_OK;
+    if (count == 0) { ix->last_write_path = 0u; return HVX_OK; }
     if (ix->is_fork) return fail(HVX_ERR_UNSUPPORTED, "rows are inserted through the handle that owns the image, not a fork");
     std::lock_guard<std::mutex> lock(ix->mu);
+    ix->last_write_path = 0u; // hvx_index_last_write_path: the batches of THIS call
     HIP_TRY(hipSetDevice(ix->device));
     DevIndex &d = ix->dev;
     if (d.dtype != HVX_F32 && d.dtype != HVX_BF16) return fail(HVX_ERR_UNSUPPORTED, "rows are inserted into f32 and bf16 images (fp8 images are read-only)");
@@ -1020,7 +1041,7 @@ extern "C" int hvx_index_upsert_batch(hvx_index *ix, const uint64_t *node_ids, c
     if (params) seq = *params;
     seq.sequential = 1; // one node at a time: the reference's order
     if (stats) memset(stats, 0, sizeof(*stats));
-    if (count == 0) return HVX_OK;
+    if (count == 0) { ix->last_write_path = 0u; return HVX_OK; }
     if (ix->is_fork) return fail(HVX_ERR_UNSUPPORTED, "rows are written through the handle that owns the image, not a fork");
     const uint32_t dim = ix->dev.dim, ld = ix->dev.ld;
     if (ix->dev.dtype != HVX_F32 && ix->dev.dtype != HVX_BF16) return fail(HVX_ERR_UNSUPPORTED, "rows are written into f32 and bf16 images");
@@ -1067,7 +1088,9 @@ extern "C" int hvx_index_upsert_batch(hvx_index *ix, const uint64_t *node_ids, c
             any = true;
         }
     }
-    auto done = [&](int rc) { (void)hipSetDevice(ix->device); (void)hipFree(d_tmp); return rc; };
+    uint32_t wpath = 0u; // hvx_index_last_write_path: the flags of every id's insert half (the delete half does not touch the word)
+    auto done = [&](int rc) { (void)hipSetDevice(ix->device); (void)hipFree(d_tmp); ix->last_write_path |= wpath; return rc; };
+    ix->last_write_path = 0u;
     uint64_t nodes = 0, batches = 0, singles = 0;
     for (uint32_t i = 0; i < count; ++i) {
         int rc;
@@ -1107,6 +1130,7 @@ extern "C" int hvx_index_upsert_batch(hvx_index *ix, const uint64_t *node_ids, c
             (*flags)[row] = 0;
             ix->dead_p = flags;
             ix->n_dead -= 1;
+            ix->last_write_path = 0u;
             if ((rc = insert_range(ix, row, 1, &lv, row, &seq, 1u, d.n, &one, bf16 ? vsrc : nullptr))) return done(rc);
             ix->desc.has_entry = 1;
             ix->desc.entry_point = ix->ids_ref()[d.entry];
@@ -1114,6 +1138,7 @@ extern "C" int hvx_index_upsert_batch(hvx_index *ix, const uint64_t *node_ids, c
             ix->publish_view();
             ix->seen_rewrite = ix->shared->rewrite_epoch.fetch_add(1, std::memory_order_acq_rel) + 1;
         }
+        wpath |= ix->last_write_path;
         nodes += 1; batches += one.batches; singles += one.single_node_batches;
     }
     if (stats) { stats->nodes = nodes; stats->batches = batches; stats->single_node_batches = singles; }

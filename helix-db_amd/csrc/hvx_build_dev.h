@@ -1,6 +1,7 @@
 // hvx_build_dev.h -- what the translation units of the device build share: the argument block of the select / link kernels, row
 // addressing, the row locks and the one-wavefront row helpers.  hvx_build.hip holds the kernels for degree limits up to 32 (one id per
-// lane, 64-bit masks) and the host side; hvx_build_wide.hip the kernels for limits up to 64 (two ids per lane, 128-bit masks).
+// lane, 64-bit masks) and the host side; hvx_build_wide.hip the kernels for limits up to 64 (two ids per lane, 128-bit masks);
+// hvx_build_wide_seq.hip the many-workgroup one-node steps for those limits.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -33,7 +34,7 @@ struct BuildArgs {
     uint32_t ldp, ncmax;        // build_link_wg_kernel: row stride of a column block in LDS (floats), candidate rows the LDS holds
     uint32_t link_ck;           // 32-float chunks per column block
     uint32_t *dbg;              // tuning builds (HVX_BUILD_DEBUG): [0] lock spins [1] prunes [2] reverse-edge removals [3] plain appends
-    float *gdm;                 // one-node steps: [layers][kSeqLayerDm] distance matrices (device-scope stores / loads)
+    float *gdm;                 // one-node steps: [layers][kSeqLayerDm] distance matrices (device-scope stores / loads; wide images: WideSeqGeom)
     uint32_t *tick;             // ... [2][layers] workgroups that have delivered (zero between launches)
     uint32_t g0, gu;            // ... workgroups of layer 0 / of every upper layer
     uint32_t kc, selw;          // wide kernels (hvx_build_wide.hip): ids per slot of cand_ids / cand_sc, of sel (the others: kCand, 32)
@@ -116,5 +117,65 @@ WideLinkGeom wide_link_geom(const DevIndex &d, uint32_t m, uint32_t m0);
 hipError_t launch_build_select_wide(const BuildArgs &a, bool fused, bool bf16, dim3 grid, hipStream_t s);
 hipError_t launch_build_link_wide(const BuildArgs &a, bool fused, bool bf16, uint32_t nodes, hipStream_t s);
 hipError_t launch_build_link_wide_wg(const BuildArgs &a, bool fused, uint32_t layers, size_t lds, hipStream_t s);
+
+// ---- ONE node into a wide image as two many-workgroup steps (hvx_build_wide_seq.hip): the wide restatement of build_select_seq_kernel /
+// build_link_seq_kernel.  Everything the two kernels and insert_range agree on is decided here, for (m, m0, layers = old max_layer + 1):
+//   the matrices in BuildArgs.gdm, layer by layer (floats; layer L starts at layer_off(L)):
+//     [0, sel_dm)                     the select's matrix: rows 0 .. hyd (row hyd: the owner's, = the search's scores), sel_rw floats wide,
+//                                     hyd <= 2 * Mmax.  128 wide where 2 * Mmax > 64 (replay_rows2<128>), 64 wide otherwise (replay_rows<64>)
+//     [sel_dm + t * link_dm, ...)     link t < Mmax: rows 0 .. nc (row nc: the owner's), kWideSeqRS floats wide, nc <= kWideSeqRow ids
+//   the pair prefix: a link whose list holds deg ids takes wide_seq_list_pairs(deg, Mmax) consecutive pair numbers, links in selection
+//     order -- (deg + 1) deg / 2 where the list exceeds its limit (all pairs among the ids and the owner), none otherwise;
+//   the grids: layer 0 takes g0 workgroups, every upper layer gu (the select step 256 threads, the link step 1 024);
+//   the link step's dynamic LDS.
+// ok = false: the shape does not fit (the one-wavefront kernels serve it).  It fits whenever the host serves the image at all: Mmax <= 64
+// on rows of at most 64 ids, m <= 32.
+constexpr uint32_t kWideSeqRow = 65;   // ids of a link's list: a row of <= 64 ids + the node
+constexpr uint32_t kWideSeqLS = 66;    // ... its stride in LDS
+constexpr uint32_t kWideSeqRS = 96;    // row stride of a link's matrix (floats): a multiple of 32 that holds 65 columns
+// removals (row, victim) one layer's links can log: <= Mmax links, each list of <= 65 ids pruned to Mmax drops <= 65 - Mmax ids, and
+// x (65 - x) <= 32 * 33 -- rows of at most 64 ids cannot overflow it
+constexpr uint32_t kWideSeqPairs = 32 * 33;
+constexpr uint32_t kWideSeqWaves = 16; // wavefronts of the link step
+constexpr uint32_t kWideSeqW2 = 128 * 2 + 128 * 4 + 128 + 64; // = kWide2Words (hvx_graph_dev.h): replay_rows2's scratch per wavefront
+__host__ __device__ __forceinline__ uint32_t wide_seq_list_pairs(uint32_t deg, uint32_t maxn) { return deg > maxn ? (deg + 1u) * deg / 2u : 0u; }
+struct WideSeqGeom {
+    uint32_t maxn[2];     // degree limit: layer 0 / upper layers
+    uint32_t sel_rw[2];   // row stride of the select's matrix
+    uint32_t sel_dm[2];   // floats of the select's matrix
+    uint32_t link_dm;     // floats of one link's matrix
+    uint32_t layer_dm[2]; // floats of one layer's matrices
+    uint32_t layers;
+    uint32_t sel_g0, sel_gu, link_g0, link_gu;
+    uint32_t link_lds;    // bytes
+    bool ok;
+    __host__ __device__ size_t layer_off(uint32_t L) const { return L == 0u ? 0u : (size_t)layer_dm[0] + (size_t)(L - 1u) * layer_dm[1]; }
+    __host__ __device__ size_t sel_off(uint32_t L) const { return layer_off(L); }
+    __host__ __device__ size_t link_off(uint32_t L, uint32_t t) const { return layer_off(L) + sel_dm[L ? 1 : 0] + (size_t)t * link_dm; }
+    __host__ __device__ size_t total_floats() const { return layer_off(layers); }
+};
+__host__ __device__ __forceinline__ WideSeqGeom wide_seq_geom(uint32_t m, uint32_t m0, uint32_t layers) {
+    WideSeqGeom g{};
+    g.maxn[0] = m0; g.maxn[1] = m;
+    g.layers = layers;
+    g.link_dm = (kWideSeqRow + 1u) * kWideSeqRS;
+    for (int u = 0; u < 2; ++u) {
+        const uint32_t hyd = 2u * g.maxn[u] < kCandWide ? 2u * g.maxn[u] : kCandWide;
+        g.sel_rw[u] = hyd > 64u ? 128u : 64u;
+        g.sel_dm[u] = (hyd + 1u) * g.sel_rw[u];
+        g.layer_dm[u] = g.sel_dm[u] + g.maxn[u] * g.link_dm;
+    }
+    // select: 32 pairs per workgroup and pass -- 8 128 pairs among 128 candidates on layer 0 (one pass of 254 workgroups), 2 016 above;
+    // link: 128 pairs per workgroup and pass -- <= 64 lists x 2 145 pairs on layer 0, <= 32 x 561 above on rows within their limit
+    g.sel_g0 = 254u; g.sel_gu = 63u;
+    g.link_g0 = 256u; g.link_gu = 32u;
+    // lists and kept lists [64][kWideSeqLS], per link: ids / ids that stay / dropped positions [4] / the neighbour, the removal log,
+    // the pair prefix, replay_rows2's scratch per wavefront
+    g.link_lds = (2u * 64u * kWideSeqLS + 64u * (2u + 4u + 1u) + 2u * kWideSeqPairs + 68u + kWideSeqWaves * kWideSeqW2) * 4u;
+    g.ok = m0 <= 64u && m <= 32u && (m0 > 32u || m > 32u) && layers >= 1u && layers <= 64u && g.link_lds <= 160u * 1024u;
+    return g;
+}
+hipError_t launch_build_select_wide_seq(const BuildArgs &a, bool fused, bool bf16, hipStream_t s);
+hipError_t launch_build_link_wide_seq(const BuildArgs &a, bool fused, bool bf16, hipStream_t s);
 
 } // namespace hvx

@@ -7,14 +7,15 @@
 //
 //   build_select_wide_kernel   select_neighbors_heuristic = select_diverse + backfill (mod.rs:809-856), one wavefront per (node, layer)
 //   build_link_wide_kernel     add_bidirectional_link (mutation.rs:1498-1583) for a node's links in selection order, one wavefront per
-//                              node: the plain restatement of the reference -- every one-node step (sequential builds, upserts,
-//                              promotions, bf16 images), Manhattan and the shapes the workgroup kernel does not serve
+//                              node: the plain restatement of the reference -- one-node steps under link_mode = 1 (the default runs the
+//                              many-workgroup steps of hvx_build_wide_seq.hip), batches over bf16 rows, Manhattan and the shapes the
+//                              workgroup kernel does not serve
 //   build_link_wide_wg_kernel  the batched link step: one 1 024-thread workgroup per link, the prune's 2 145 pairwise distances
 //                              evaluated eagerly from LDS -- the wide twin of build_link_wg_kernel (batches of fewer than 1 024 nodes and
 //                              hvx_index_link_rows; larger batches link faster with build_link_wide_kernel: insert_range)
 //
 // Distances between two resident rows are pair_distance (hvx_graph_dev.h): the reference's summation order over f32 rows of every
-// metric and tree, and over bf16 rows (BF), so bf16 images take one-node inserts through the same two one-wavefront kernels.
+// metric and tree, and over bf16 rows (BF), so bf16 images run the same two one-wavefront kernels.
 // Every row is read and written with agent-scope atomics (ld_row / st_row) and every lock in this file is the relaxed exchange +
 // s_waitcnt of build_link_wg_kernel: no kernel here carries an agent-scope acquire / release (an L2 invalidate / write-back per lock).
 #include <hip/hip_runtime.h>

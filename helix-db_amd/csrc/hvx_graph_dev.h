@@ -323,11 +323,17 @@ __device__ __forceinline__ void store_canonical_reg(uint32_t *row, uint32_t stri
 // scale_contracts.rs:167-173): two candidates per lane (c = lane, lane + 64), 128-bit masks, the matrix rows STREAMED (32 floats at a
 // time: only "closer than the owner" bits are kept), Candidate order and the masks in rank order through LDS.  RW = row width of G in
 // floats, a multiple of 32.  W2: per-wavefront scratch of kWide2Words uint32 (keys [128] u64 | conf [128][4] | ord [128] | kept [64]).
+//   * `alive` (two words, list positions 0..63 / 64..127; null = every id): as replay_rows' -- an id that has left the list since the matrix
+//     was evaluated ranks behind every live id, rejects nobody and is neither selected nor backfilled; `dropped` (two words, null = not
+//     wanted) = the live ids that do not stay, by list position.  Both are resolved at compile time: a call without them is the code it was.
 constexpr uint32_t kWide2Words = 128 * 2 + 128 * 4 + 128 + 64;
+constexpr uint32_t kWide2Kept = 128 * 2 + 128 * 4 + 128; // where the kept list starts in W2
 template <int RW>
-__device__ __forceinline__ uint32_t replay_rows2(const float *G, const uint32_t *cur, uint32_t nc, uint32_t maxn, uint32_t lane, uint32_t *W2, bool *bad) {
+__device__ __forceinline__ uint32_t replay_rows2(const float *G, const uint32_t *cur, uint32_t nc, uint32_t maxn, uint32_t lane, uint32_t *W2, bool *bad,
+                                                 const unsigned long long *alive = nullptr, unsigned long long *dropped = nullptr) {
     unsigned long long *keys = reinterpret_cast<unsigned long long *>(W2);
-    uint32_t *conf = W2 + 256, *ord = W2 + 256 + 512, *kept = W2 + 256 + 512 + 128;
+    uint32_t *conf = W2 + 256, *ord = W2 + 256 + 512, *kept = W2 + kWide2Kept;
+    const bool masked = alive != nullptr;
     float d[2];
     uint32_t v[2], rank[2];
     unsigned long long key[2];
@@ -335,7 +341,7 @@ __device__ __forceinline__ uint32_t replay_rows2(const float *G, const uint32_t 
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
         const uint32_t c = lane + 64u * (uint32_t)s;
-        const bool valid = c < nc;
+        const bool valid = c < nc && (!masked || ((alive[s] >> lane) & 1ull) != 0ull);
         d[s] = valid ? ld_agent(G + (size_t)nc * RW + c) : 0.f;
         v[s] = valid ? cur[c] : kSentinel;
         float chk = d[s];
@@ -351,8 +357,13 @@ __device__ __forceinline__ uint32_t replay_rows2(const float *G, const uint32_t 
         rank[0] += kt < key[0] ? 1u : 0u;
         rank[1] += kt < key[1] ? 1u : 0u;
     }
-    const unsigned long long alo = nc >= 64u ? ~0ull : (1ull << nc) - 1ull;
-    const unsigned long long ahi = nc <= 64u ? 0ull : (nc >= 128u ? ~0ull : (1ull << (nc - 64u)) - 1ull);
+    unsigned long long alo = nc >= 64u ? ~0ull : (1ull << nc) - 1ull;
+    unsigned long long ahi = nc <= 64u ? 0ull : (nc >= 128u ? ~0ull : (1ull << (nc - 64u)) - 1ull);
+    if (masked) { alo &= alive[0]; ahi &= alive[1]; }
+    // the live ids hold the first nlive ranks
+    const uint32_t nlive = masked ? (uint32_t)__builtin_popcountll(alo) + (uint32_t)__builtin_popcountll(ahi) : nc;
+    const unsigned long long vlo = !masked ? alo : (nlive >= 64u ? ~0ull : (1ull << nlive) - 1ull);
+    const unsigned long long vhi = !masked ? ahi : (nlive <= 64u ? 0ull : (nlive >= 128u ? ~0ull : (1ull << (nlive - 64u)) - 1ull));
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
         const uint32_t c = lane + 64u * (uint32_t)s;
@@ -377,7 +388,7 @@ __device__ __forceinline__ uint32_t replay_rows2(const float *G, const uint32_t 
             else if (ch == 2) hi |= bits;
             else if (ch == 3) hi |= bits << 32;
         }
-        lo &= alo; hi &= ahi;
+        lo &= alo; hi &= ahi; // (columns past nc hold no distance; an id that has left rejects nobody)
         if (c < 64u) lo &= ~(1ull << c); else hi &= ~(1ull << (c - 64u));
         const uint32_t r = rank[s];
         conf[r * 4u + 0u] = (uint32_t)lo; conf[r * 4u + 1u] = (uint32_t)(lo >> 32);
@@ -387,7 +398,7 @@ __device__ __forceinline__ uint32_t replay_rows2(const float *G, const uint32_t 
     lds_order();
     unsigned long long slo = 0ull, shi = 0ull, rlo = 0ull, rhi = 0ull; // selected by index / by rank
     uint32_t ns = 0;
-    for (uint32_t r = 0; r < nc && ns < maxn; ++r) {
+    for (uint32_t r = 0; r < nlive && ns < maxn; ++r) {
         const unsigned long long clo = ((unsigned long long)conf[r * 4u + 1u] << 32) | conf[r * 4u + 0u];
         const unsigned long long chi = ((unsigned long long)conf[r * 4u + 3u] << 32) | conf[r * 4u + 2u];
         if ((clo & slo) | (chi & shi)) continue;
@@ -399,23 +410,40 @@ __device__ __forceinline__ uint32_t replay_rows2(const float *G, const uint32_t 
     // rank r = lane, lane + 64: the selected ones to their slots in selection order, then the backfill: the others, closest first
     const unsigned long long lt = (1ull << lane) - 1ull;
     const uint32_t nsel = ns;
-    const unsigned long long flo = ~rlo & alo, fhi = ~rhi & ahi; // (the live ids hold the first nc ranks)
+    const unsigned long long flo = ~rlo & vlo, fhi = ~rhi & vhi;
     const uint32_t nfree = (uint32_t)__builtin_popcountll(flo) + (uint32_t)__builtin_popcountll(fhi);
+    bool leaves[2] = {false, false}; // a live id that does not stay
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
         const uint32_t r = lane + 64u * (uint32_t)s;
-        if (r >= nc) continue;
+        if (r >= nlive) continue;
         const uint32_t id = cur[ord[r]];
         const bool sel = s == 0 ? ((rlo >> lane) & 1ull) != 0ull : ((rhi >> lane) & 1ull) != 0ull;
         if (sel) {
             const uint32_t slot = s == 0 ? (uint32_t)__builtin_popcountll(rlo & lt) : (uint32_t)__builtin_popcountll(rlo) + (uint32_t)__builtin_popcountll(rhi & lt);
             kept[slot] = id;
-        } else if (nsel < maxn) {
-            const uint32_t rk = s == 0 ? (uint32_t)__builtin_popcountll(flo & lt) : (uint32_t)__builtin_popcountll(flo) + (uint32_t)__builtin_popcountll(fhi & lt);
-            if (nsel + rk < maxn) kept[nsel + rk] = id;
+        } else {
+            leaves[s] = true;
+            if (nsel < maxn) {
+                const uint32_t rk = s == 0 ? (uint32_t)__builtin_popcountll(flo & lt) : (uint32_t)__builtin_popcountll(flo) + (uint32_t)__builtin_popcountll(fhi & lt);
+                if (nsel + rk < maxn) { kept[nsel + rk] = id; leaves[s] = false; }
+            }
         }
     }
     if (nsel < maxn) ns = nsel + nfree < maxn ? nsel + nfree : maxn;
+    if (dropped) { // by list position (ord[r] = the position of the id ranked r): few -- a row over its limit by one loses one
+        unsigned long long dlo = 0ull, dhi = 0ull;
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            unsigned long long dr = __ballot(leaves[s]);
+            while (dr) {
+                const uint32_t c = ord[(uint32_t)__builtin_ctzll(dr) + 64u * (uint32_t)s];
+                dr &= dr - 1ull;
+                if (c < 64u) dlo |= 1ull << c; else dhi |= 1ull << (c - 64u);
+            }
+        }
+        dropped[0] = dlo; dropped[1] = dhi;
+    }
     lds_order();
     return ns;
 }

@@ -169,6 +169,8 @@ OPT_HNSW_GENERAL_KERNEL, OPT_WAVE_LOG2CAP, OPT_FLAT_FORCE_VALU, OPT_FLAT_FIRST_C
     OPT_RESTRICTED_EXACT_MIB, OPT_FLAT_NO_TAIL, OPT_HNSW_SHADOW_PRUNE = range(15)
 PATH_VALU, PATH_MFMA_128, PATH_TILE_256, PATH_FILTERED, PATH_FULL_SPLIT, PATH_VALU_FALLBACK_QUERIES, PATH_WIDENED, \
     PATH_PAIR_OVERFLOW_REPEAT, PATH_SMALL_BATCH, PATH_DIRECT, PATH_EXACT_TAIL = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024
+# hvx_write_path flags: which kernels linked the nodes of a handle's last build / insert / upsert call (last_write_path)
+WRITE_EAGER_STEPS, WRITE_ONE_WAVE, WRITE_LINK_WG, WRITE_WIDE = 1, 2, 4, 8
 # hvx_restricted_strategy: AUTO = the DEVICE's plan (exact scan while the candidate rows take <= 1 GiB, round 6), REFERENCE_PLAN = the
 # reference's (restricted.rs:426-453: exact <= 256 ids / 4 MiB, the filter-aware walk above)
 RESTRICTED_AUTO, RESTRICTED_EXACT, RESTRICTED_FILTERED, RESTRICTED_REFERENCE_PLAN = 0, 1, 2, 3
@@ -967,6 +969,12 @@ class ValidatedVectorReadIndex:
         lib().hvx_index_last_scan_path.restype = C.c_uint32
         lib().hvx_index_last_scan_path.argtypes = [_vp]
         return int(lib().hvx_index_last_scan_path(self._h))
+
+    def last_write_path(self) -> int:
+        """hvx_write_path flags of this handle's last build / insert_batch / upsert_batch call (0: it linked nothing)"""
+        lib().hvx_index_last_write_path.restype = C.c_uint32
+        lib().hvx_index_last_write_path.argtypes = [_vp]
+        return int(lib().hvx_index_last_write_path(self._h))
 
     def set_occupancy(self, queries_per_simd: int):
         _check(lib().hvx_index_set_occupancy(self._h, queries_per_simd))

@@ -677,7 +677,7 @@ int hvx_hydrator_finish_reserve(const hvx_hydrator *, const hvx_index_desc *tmpl
  * insertion of the rounded vectors row for row, the default runs batches exactly as over f32 rows (the link step widens bf16 column
  * blocks into LDS: half the bytes of an f32 build).  Served: what the bf16 import and the unrolled build search serve -- cosine /
  * Euclidean, the AVX+FMA tree, dim in {128,256,384,512,768,1024,1536}, max(ef_construction, m0, 2 m) <= 352, m0 <= 64 (above 32: the
- * one-wavefront kernels of csrc/hvx_build_wide.hip link every batch); anything else, and HVX_FP8_E4M3: HVX_ERR_UNSUPPORTED before
+ * one-wavefront kernels of csrc/hvx_build_wide.hip link every batch of more than one node); anything else, and HVX_FP8_E4M3: HVX_ERR_UNSUPPORTED before
  * anything is allocated.  Peak memory is the f32 staging copy plus the bf16 rows until packing ends.
  */
 enum hvx_build_batching {    /* hvx_build_params.sequential */
@@ -694,7 +694,9 @@ typedef struct hvx_build_params {
     uint32_t link_mode;       /* batched link step: 0 => one workgroup per link with the prune evaluated from LDS whenever the rows fit
                                  (Mmax + 2 rows of ld floats <= 160 KB), 1 => one wavefront per node (links one after the other).
                                  One node at a time (sequential = 1, upserts, promotions): 0 => its select and its links as two many-workgroup
-                                 steps with every prune's distance matrix evaluated up front (round 6), 1 => the one-wavefront kernels */
+                                 steps with every prune's distance matrix evaluated up front, on narrow images (round 6) and on images with
+                                 degree limits above 32 alike (csrc/hvx_build_wide_seq.hip; f32 and bf16 rows), 1 => the one-wavefront kernels.
+                                 hvx_index_last_write_path reports which of them a call ran */
     uint32_t scatter;         /* 1 => batched mode inserts in the order (i * stride) mod n, stride ~ 0.618 n coprime with n, instead of
                                  id order.  For rows whose order follows the data (dumps sorted by topic, indexes hydrated in key order):
                                  the nodes of one batch do not see each other, and consecutive rows of such data are each other's
@@ -706,6 +708,16 @@ typedef struct hvx_build_stats {
     uint64_t nodes, batches, single_node_batches;
 } hvx_build_stats;
 void hvx_build_params_default(hvx_build_params *);
+/* which kernels linked the nodes of the handle's last hvx_index_build / hvx_index_insert_batch / hvx_index_upsert_batch call (bit flags,
+ * accumulated over the batches of that call; a build reports on the handle it returns).  0: the call linked nothing (no node, or only the
+ * first node of an empty image).  Deletes -- the delete half of an upsert included -- do not touch the word. */
+enum hvx_write_path {
+    HVX_WRITE_EAGER_STEPS = 1,  /* one node: select and links as two many-workgroup steps, matrices evaluated up front */
+    HVX_WRITE_ONE_WAVE   = 2,   /* one wavefront per node (lazy select_diverse) */
+    HVX_WRITE_LINK_WG    = 4,   /* batched link step, one workgroup per link */
+    HVX_WRITE_WIDE       = 8    /* the two-ids-per-lane kernels (degree limits above 32) */
+};
+uint32_t hvx_index_last_write_path(const hvx_index *);
 int hvx_index_build(const hvx_index_desc *desc, const uint64_t *node_ids, const float *vectors /*host or device*/,
                     const uint16_t *levels /*[n] or NULL = all layer 0*/, const hvx_build_params *params, hvx_index **out,
                     hvx_build_stats *stats /*nullable*/);
