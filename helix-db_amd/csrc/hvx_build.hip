@@ -520,6 +520,7 @@ static BuildKernels pick_build_kernels(uint32_t metric, bool fused, bool bf16 = 
 static bool one_node_batches(const hvx_build_params *p) { return p->sequential != HVX_BUILD_AUTO && p->sequential != HVX_BUILD_BATCHED; }
 
 extern "C" uint32_t hvx_index_last_write_path(const hvx_index *ix) { return ix ? ix->last_write_path : 0u; }
+extern "C" uint32_t hvx_index_last_write_tie_overflows(const hvx_index *ix) { return ix ? ix->last_write_tie_overflows : 0u; }
 
 extern "C" void hvx_build_params_default(hvx_build_params *p) {
     if (!p) return;
@@ -643,7 +644,8 @@ static int insert_range(hvx_index *ix, uint64_t first, uint64_t count, const uin
         if (hipMemsetAsync(d_dbg, 0, 32, s) != hipSuccess) return sbail2(fail(HVX_ERR_DEVICE, "memset"));
     }
     hipLaunchKernelGGL(iota_kernel, dim3((uint32_t)((count + 255) / 256)), dim3(256), 0, s, d_iota, (uint32_t)count, (uint32_t)first, stride, (uint32_t)std::max<uint64_t>(mod, 1));
-    if (hipMemsetAsync(d_err, 0, 4, s) != hipSuccess) return sbail2(fail(HVX_ERR_DEVICE, "memset"));
+    uint32_t *d_ties = d_err + 1; // nodes whose build search stayed flagged (the word next to the error word: one read for both)
+    if (hipMemsetAsync(d_err, 0, 8, s) != hipSuccess) return sbail2(fail(HVX_ERR_DEVICE, "memset"));
 
     uint32_t *l0w = const_cast<uint32_t *>(d.l0), *upw = const_cast<uint32_t *>(d.up);
     const bool fused = kernel_fused(d.fkernel);
@@ -713,6 +715,7 @@ static int insert_range(hvx_index *ix, uint64_t first, uint64_t count, const uin
         a.out_counts = b_cnt;
         a.out_status = d_status;
         a.tie_flags = ix->d_tie;
+        a.tie_count = d_ties; // (a flagged build search is counted, never repeated: hvx_index_last_write_tie_overflows)
         a.build_nodes = d_iota + (done - first);
         if (bf16 && build_q) a.queries = build_q + (size_t)(done - first) * d.dim;
         else if (bf16) {
@@ -814,9 +817,11 @@ static int insert_range(hvx_index *ix, uint64_t first, uint64_t count, const uin
     }
     if (hipStreamSynchronize(s2) != hipSuccess) return sbail2(fail(HVX_ERR_DEVICE, "build did not complete: %s", hipGetErrorString(hipGetLastError())));
     drop_streams();
-    uint32_t err = 0;
-    if (hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+    uint32_t words[2] = {0u, 0u}; // the error word, the flagged nodes
+    if (hipMemcpyAsync(words, d_err, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
         return sbail(fail(HVX_ERR_DEVICE, "build did not complete: %s", hipGetErrorString(hipGetLastError())));
+    const uint32_t err = words[0];
+    ix->last_write_tie_overflows += words[1];
     if (d_dbg) {
         uint32_t h[8] = {0};
         (void)hipMemcpy(h, d_dbg, 32, hipMemcpyDeviceToHost);
@@ -913,10 +918,11 @@ extern "C" int hvx_index_insert_batch(hvx_index *ix, const uint64_t *node_ids, c
     hvx_build_params_default(&dflt);
     if (!params) params = &dflt;
     if (stats) memset(stats, 0, sizeof(*stats));
-    if (count == 0) { ix->last_write_path = 0u; return HVX_OK; }
+    if (count == 0) { ix->last_write_path = 0u; ix->last_write_tie_overflows = 0u; return HVX_OK; }
     if (ix->is_fork) return fail(HVX_ERR_UNSUPPORTED, "rows are inserted through the handle that owns the image, not a fork");
     std::lock_guard<std::mutex> lock(ix->mu);
     ix->last_write_path = 0u; // hvx_index_last_write_path: the batches of THIS call
+    ix->last_write_tie_overflows = 0u;
     HIP_TRY(hipSetDevice(ix->device));
     DevIndex &d = ix->dev;
     if (d.dtype != HVX_F32 && d.dtype != HVX_BF16) return fail(HVX_ERR_UNSUPPORTED, "rows are inserted into f32 and bf16 images (fp8 images are read-only)");
@@ -1041,7 +1047,7 @@ extern "C" int hvx_index_upsert_batch(hvx_index *ix, const uint64_t *node_ids, c
     if (params) seq = *params;
     seq.sequential = 1; // one node at a time: the reference's order
     if (stats) memset(stats, 0, sizeof(*stats));
-    if (count == 0) { ix->last_write_path = 0u; return HVX_OK; }
+    if (count == 0) { ix->last_write_path = 0u; ix->last_write_tie_overflows = 0u; return HVX_OK; }
     if (ix->is_fork) return fail(HVX_ERR_UNSUPPORTED, "rows are written through the handle that owns the image, not a fork");
     const uint32_t dim = ix->dev.dim, ld = ix->dev.ld;
     if (ix->dev.dtype != HVX_F32 && ix->dev.dtype != HVX_BF16) return fail(HVX_ERR_UNSUPPORTED, "rows are written into f32 and bf16 images");
@@ -1088,9 +1094,10 @@ extern "C" int hvx_index_upsert_batch(hvx_index *ix, const uint64_t *node_ids, c
             any = true;
         }
     }
-    uint32_t wpath = 0u; // hvx_index_last_write_path: the flags of every id's insert half (the delete half does not touch the word)
-    auto done = [&](int rc) { (void)hipSetDevice(ix->device); (void)hipFree(d_tmp); ix->last_write_path |= wpath; return rc; };
+    uint32_t wpath = 0u, wties = 0u; // hvx_index_last_write_path / _tie_overflows: over every id's insert half (the delete half touches neither)
+    auto done = [&](int rc) { (void)hipSetDevice(ix->device); (void)hipFree(d_tmp); ix->last_write_path |= wpath; ix->last_write_tie_overflows = wties; return rc; };
     ix->last_write_path = 0u;
+    ix->last_write_tie_overflows = 0u;
     uint64_t nodes = 0, batches = 0, singles = 0;
     for (uint32_t i = 0; i < count; ++i) {
         int rc;
@@ -1131,6 +1138,7 @@ extern "C" int hvx_index_upsert_batch(hvx_index *ix, const uint64_t *node_ids, c
             ix->dead_p = flags;
             ix->n_dead -= 1;
             ix->last_write_path = 0u;
+            ix->last_write_tie_overflows = 0u;
             if ((rc = insert_range(ix, row, 1, &lv, row, &seq, 1u, d.n, &one, bf16 ? vsrc : nullptr))) return done(rc);
             ix->desc.has_entry = 1;
             ix->desc.entry_point = ix->ids_ref()[d.entry];
@@ -1139,6 +1147,7 @@ extern "C" int hvx_index_upsert_batch(hvx_index *ix, const uint64_t *node_ids, c
             ix->seen_rewrite = ix->shared->rewrite_epoch.fetch_add(1, std::memory_order_acq_rel) + 1;
         }
         wpath |= ix->last_write_path;
+        wties += ix->last_write_tie_overflows;
         nodes += 1; batches += one.batches; singles += one.single_node_batches;
     }
     if (stats) { stats->nodes = nodes; stats->batches = batches; stats->single_node_batches = singles; }

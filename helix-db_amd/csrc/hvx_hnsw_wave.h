@@ -1113,6 +1113,8 @@ __device__ __forceinline__ void hnsw_wave_query(const HnswArgs &a, const uint32_
         if (a.out_status) a.out_status[q] = bad_score ? 8u /*HVX_ERR_INVARIANT*/ : 0u;
         if (a.qstats) a.qstats[q] = hvx_query_stats{st_exp, st_nb, st_vl, st_dc};
         if (a.tie_flags) a.tie_flags[q] = tie_overflow ? 1u : 0u;
+        // a build search that did: its rows are not proven equal to the reference's (one count per node, read where the call reads its error word)
+        if (BUILD && tie_overflow && a.tie_count) atomicAdd(a.tie_count, 1u);
         // a query whose beam evicted equal-score candidates beyond its slack joins the re-run list (launch_hnsw_wave)
         if (!BUILD && tie_overflow && a.rerun_ctl && !a.only_flagged) a.rerun_list[atomicAdd(&a.rerun_ctl[0], 1u)] = q;
         if (AD && ST && a.ad.stats) {

@@ -85,6 +85,7 @@ struct hvx_index {
     uint32_t opt[HVX_OPT_COUNT] = {}; // execution-path selectors (hvx_index_set_option); 0 = the library's own choice
     uint32_t last_scan_path = 0;     // hvx_scan_path flags of the handle's last exact scan (hvx_index_last_scan_path)
     uint32_t last_write_path = 0;    // hvx_write_path flags of the handle's last build / insert / upsert call (hvx_index_last_write_path)
+    uint32_t last_write_tie_overflows = 0; // ... and its nodes whose build search stayed flagged (hvx_index_last_write_tie_overflows)
     bool bitmap_dirty = false;       // d_bitmap holds stale visited bits (general kernel ran last)
     hipStream_t stream = nullptr;      // stream in use
     hipStream_t own_stream = nullptr;  // created at import

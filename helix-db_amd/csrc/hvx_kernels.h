@@ -51,6 +51,8 @@ struct HnswArgs {
     uint32_t adaptive;         // 0 = strict-exhaustive search; 1 = non-strict arms, policy in `ad`
     const uint32_t *build_nodes; // BUILD instantiations (hvx_build.hip): [b] internal ids of the nodes being inserted (their rows are the queries)
     uint32_t build_ef_upper;   // ... beam width on the layers above 0 (ef is layer 0's)
+    uint32_t *tie_count;       // ... one device word, nullable: + 1 for every node whose search evicted an equal-score candidate past the
+                               //     beam's slack (hvx_index_last_write_tie_overflows)
     uint32_t only_flagged;     // wave kernel: 1 = the re-run launch -- only queries whose tie flag is set do anything (with a wider beam)
     uint32_t occupancy;        // wave kernel: 2 = the two-queries-per-SIMD build (callers with >= 2 batches in flight), else 1
     uint32_t pair;             // 1 = the owner / gatherer kernel (hvx_hnsw_pair.h) where it serves the launch

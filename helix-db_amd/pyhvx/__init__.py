@@ -976,6 +976,13 @@ class ValidatedVectorReadIndex:
         lib().hvx_index_last_write_path.argtypes = [_vp]
         return int(lib().hvx_index_last_write_path(self._h))
 
+    def last_write_tie_overflows(self) -> int:
+        """nodes of this handle's last build / insert / upsert call whose build search evicted an equal-score candidate past its
+        beam's slack: 0 = the call's rows are proven equal to the reference's sequential insertion (one-node mode)"""
+        lib().hvx_index_last_write_tie_overflows.restype = C.c_uint32
+        lib().hvx_index_last_write_tie_overflows.argtypes = [_vp]
+        return int(lib().hvx_index_last_write_tie_overflows(self._h))
+
     def set_occupancy(self, queries_per_simd: int):
         _check(lib().hvx_index_set_occupancy(self._h, queries_per_simd))
 

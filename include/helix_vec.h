@@ -663,7 +663,8 @@ int hvx_hydrator_finish_reserve(const hvx_hydrator *, const hvx_index_desc *tmpl
  * for batches of consecutive nodes.  `levels[i]` = the node's top layer (drawn by the host with select_layer_from_uniform,
  * mod.rs:776-796 -- the reference's draw is intentionally non-deterministic, randomness.rs:41-46).  Nodes are inserted in
  * node-id order.  With params->sequential = HVX_BUILD_ONE_NODE every batch holds ONE node and the graph equals the reference's sequential
- * insertion row for row; otherwise a batch holds up to min(max_batch, inserted / batch_divisor) nodes that do not see each
+ * insertion row for row -- provided hvx_index_last_write_tie_overflows returns 0 for the call (tie-heavy corpora: see there); otherwise
+ * a batch holds up to min(max_batch, inserted / batch_divisor) nodes that do not see each
  * other (a node above the current top layer is always inserted alone and becomes the entry point).  The result is an
  * ordinary searchable hvx_index; hvx_index_export_graph hands the rows back for the host to persist (values/vectors.rs).
  * Served shapes: f32 rows of any dimension, cosine / Euclidean / Manhattan, every summation tree of the reference's float kernels
@@ -718,6 +719,18 @@ enum hvx_write_path {
     HVX_WRITE_WIDE       = 8    /* the two-ids-per-lane kernels (degree limits above 32) */
 };
 uint32_t hvx_index_last_write_path(const hvx_index *);
+/*
+ * The precondition of every "row for row" promise of hvx_index_build / hvx_index_insert_batch / hvx_index_upsert_batch: a build search
+ * keeps its beam in registers, max(ef_construction, 2 m, m0) entries plus a slack of at least 32 for candidates that tie with the worst
+ * entry (the reference keeps such candidates in an unbounded queue).  A corpus with masses of EQUAL distances -- duplicated rows, one-hot
+ * or count features, coarsely quantised embeddings, zero vectors -- can evict an equal-score candidate past that slack: more than 32
+ * strictly closer rows have to enter a beam that is full of ties.  Such a node is linked from the candidates it has and is COUNTED (the
+ * search is not repeated): this accessor returns the number of such nodes of the handle's last build / insert / upsert call (a build
+ * reports on the handle it returns; an upsert the sum over its ids; 0 after a call that linked nothing; deletes do not touch it).
+ * 0: every node's candidates are the reference's, and one node at a time the rows equal the reference's sequential insertion.
+ * > 0: equality with the reference is NOT proven for that call (the graph is still a valid HNSW graph: hvx_index_audit_graph).
+ */
+uint32_t hvx_index_last_write_tie_overflows(const hvx_index *);
 int hvx_index_build(const hvx_index_desc *desc, const uint64_t *node_ids, const float *vectors /*host or device*/,
                     const uint16_t *levels /*[n] or NULL = all layer 0*/, const hvx_build_params *params, hvx_index **out,
                     hvx_build_stats *stats /*nullable*/);
@@ -730,8 +743,8 @@ int hvx_index_build(const hvx_index_desc *desc, const uint64_t *node_ids, const 
  * limits m0 <= 64 / m <= 32 on rows of at most 64 ids as hvx_index_build serves them (above: HVX_ERR_UNSUPPORTED, nothing changed),
  * validated like imported rows (an invalid vector fails the call before anything changes), given headers and -- when SimHash
  * rows are attached -- SimHash rows, and linked into the graph by the loop hvx_index_build runs: params->sequential = 1 is the
- * reference's insertion row for row (tests/test_gpu_build.py), the batched mode trades that for throughput exactly as the build
- * does.  params = NULL: the defaults.  The call goes through the handle that owns the image; when it returns the new generation
+ * reference's insertion row for row (tests/test_gpu_build.py; precondition: hvx_index_last_write_tie_overflows returns 0), the
+ * batched mode trades that for throughput exactly as the build does.  params = NULL: the defaults.  The call goes through the handle that owns the image; when it returns the new generation
  * is visible on that handle (hvx_index_visible_seq + 1, hvx_index_rows grown) and every fork adopts it with hvx_index_refresh --
  * the host's registry decides when (read_index.rs:55-61: a resident copy serves a snapshot only when its sequence matches).
  * Forks may keep searching during the call: they see their own generation's entry point, and neighbour rows as stale-or-current,
@@ -771,7 +784,8 @@ int hvx_index_delete_batch(hvx_index *, const uint64_t *node_ids /*[count]*/, ui
  * and every id tie-break stays the reference's -- or appended when the id is above every id of the image (levels[i], NULL = 0, is
  * used there; a revived node keeps the level of its slot: the reference's level draw is random, any draw is a valid one).  Every
  * vector is validated before anything changes.  HVX_ERR_UNSUPPORTED for an id that lies between the image's ids without a slot.
- * Rows equal the oracle's delete + insert of the same ids (tests/test_gpu_delete.py).
+ * Rows equal the oracle's delete + insert of the same ids (tests/test_gpu_delete.py) whenever hvx_index_last_write_tie_overflows
+ * returns 0 for the call (the sum over the insert halves of its ids).
  * bf16 images (round 6): the new vector is rounded to bf16, validated and linked over the bf16 rows (== the oracle on the rounded vectors);
  * appended ids need spare rows (hvx_index_import_reserve).  fp8 images are read-only.  Degree limits as hvx_index_insert_batch
  * (m0 <= 64, m <= 32; f32 and bf16 images alike), checked before the delete half runs.

@@ -597,3 +597,136 @@ def guarded_half_cosine_model(data: np.ndarray, q: np.ndarray, flush: bool = Fal
         c = np.where(c < -1, np.float32(-1), np.where(c > 1, np.float32(1), c))
         s = ((np.float32(1) - c) * np.float32(0.5)).astype(np.float32)
     return np.where(has, s, np.float32(0)), has
+
+
+# ---- tie-heavy corpora for the write path (test_tie_fixtures.py, test_gpu_build_ties.py) ----
+# Gaussian rows never give two equal distances, so the (score, id) order of the beam, the strict < of select_diverse and the slack of
+# the device's register beam decide nothing on them.  These rows have a handful of distinct distances among thousands of pairs.
+
+def lattice_rows(n: int, dim: int, nz: int, seed: int, support: int = 0) -> np.ndarray:
+    """n DISTINCT rows with exactly nz entries of +-1 and zeros elsewhere (support > 0: all of them within the first `support` coordinates
+    -- a denser lattice: more rows share a coordinate, so more rows lie strictly closer than the mass of ties).  Every product and partial sum of a distance between two of them
+    is a small integer, exact under every metric, summation tree and fused or unfused multiply-add (L2: even integers 2 .. 4 nz, cosine:
+    (1 - j / nz) / 2 with one correctly rounded division); round_bf16 is the identity on them."""
+    rng = np.random.default_rng(seed)
+    seen, out = set(), np.zeros((n, dim), np.float32)
+    i = 0
+    while i < n:
+        pos = np.sort(rng.choice(support or dim, nz, replace=False))
+        sign = rng.integers(0, 2, nz) * 2 - 1
+        key = (tuple(pos.tolist()), tuple(sign.tolist()))
+        if key in seen:
+            continue
+        seen.add(key)
+        out[i, pos] = sign
+        i += 1
+    return out
+
+
+def duplicate_groups(groups, copies, filler: int, dim: int, seed: int):
+    """Exact copies of `groups` lattice points (nz 2), copies[g] of point g, plus `filler` further distinct lattice rows, shuffled.
+    Rows of a group tie at distance 0 with each other and at equal distances with everything else.
+    Returns (rows, label per row: the group's number, -1 for a filler row)."""
+    copies = [copies] * groups if np.isscalar(copies) else list(copies)
+    assert len(copies) == groups
+    base = lattice_rows(groups + filler, dim, 2, seed)
+    rows = np.concatenate([np.repeat(base[:groups], copies, axis=0), base[groups:]])
+    label = np.concatenate([np.repeat(np.arange(groups), copies), np.full(filler, -1)]).astype(np.int64)
+    perm = np.random.default_rng(seed + 1).permutation(rows.shape[0])
+    return np.ascontiguousarray(rows[perm]), label[perm]
+
+
+def tie_prone_inserts(orc, oix_factory, data, ids, levels, efc: int, beam: int):
+    """The oracle's sequential insertion of the rows into oix_factory()'s index.  Before insert i it counts the inserts that a register
+    beam of `beam` entries cannot hold without evicting an equal-score candidate: the oracle's search(data[i], efc, efc) over the rows
+    inserted so far is full (efc results) AND more than `beam` of those rows score at or under the worst entry of that W (oix.flat, the
+    exact scan in the same arithmetic).  Returns (the oracle index, that count)."""
+    oix = oix_factory()
+    prone = 0
+    for i in range(data.shape[0]):
+        if i > beam:
+            rc, _, wsc = oix.search(data[i], efc, efc)
+            assert rc == orc.OK
+            if wsc.size == efc:
+                rc, _, fsc = oix.flat(data[i], beam + 1)
+                assert rc == orc.OK
+                prone += int(fsc.size > beam and fsc[beam] <= wsc[-1])
+        assert oix.insert(int(ids[i]), data[i], int(levels[i])) == orc.OK
+    return oix, prone
+
+
+def unreachable_l0(ex) -> int:
+    """rows of an oracle export that a walk over layer 0 from the entry point does not reach"""
+    ids = ex["node_ids"].tolist()
+    if not ids:
+        return 0
+    pos = {nid: t for t, nid in enumerate(ids)}
+    off, nb = ex["l0_offsets"], ex["l0_neighbors"]
+    seen = {pos[int(ex["entry_point"])]}
+    stack = list(seen)
+    while stack:
+        t = stack.pop()
+        for x in nb[int(off[t]):int(off[t + 1])].tolist():
+            u = pos[x]
+            if u not in seen:
+                seen.add(u)
+                stack.append(u)
+    return len(ids) - len(seen)
+
+
+TIE_BEAM = 192  # the register beam of the build searches at max(ef_construction, 2 M) <= 160: 64 * 3 entries
+# name -> (corpus, n, dim, nz, metric, m, m0, ef_construction, oracle kernel name, level multiplier, min tie-prone inserts, min full rows)
+# corpus "lattice": lattice_rows(n, dim, nz, seed 1), "lattice32": the same with support 32; "dup": duplicate_groups(2, [20, 80], n - 100, dim, seed 5).  metric: 0 cosine,
+# 1 squared Euclidean, 2 Manhattan.  Full rows (layer-0 rows with m0 ids): >= 100 where the prune is the point of the case, >= 50 on the
+# M 32 / M0 64 cases (<= 400 rows for the oracle's time: ~60 rows reach 64 ids), so that the 65-id prune runs under ties there too.
+TIE_CASES = {
+    "l2_efc160":   ("lattice", 1200, 128, 2, 1, 16, 32, 160, "avx_fma", 16, 100, 0),
+    # non-zeros within 32 coordinates: ~70 rows at distance 2 from each row under ~1 000 at distance 4.  A full W of 4s then admits more
+    # than 32 closer rows, which is what makes the DEVICE's 192-entry beam evict a tie (the count above says only that the ties exist)
+    "l2_dense":    ("lattice32", 1200, 128, 2, 1, 16, 32, 160, "avx_fma", 16, 100, 0),
+    "l2_prune":    ("lattice", 1200, 128, 3, 1, 16, 32, 100, "avx_fma", 16, 100, 100),
+    "l2_small":    ("lattice", 380, 128, 2, 1, 16, 32, 160, "avx_fma", 16, 100, 0),
+    "cos_small":   ("lattice", 380, 128, 2, 0, 16, 32, 160, "avx_fma", 16, 100, 0),
+    "cos_prune":   ("lattice", 1200, 128, 3, 0, 16, 32, 100, "avx_fma", 16, 100, 100),
+    "wide":        ("lattice", 380, 128, 2, 1, 32, 64, 160, "avx_fma", 32, 100, 50),
+    "scalar_100":  ("lattice", 600, 100, 2, 1, 16, 32, 100, "scalar", 16, 100, 0),
+    "l1_prune":    ("lattice", 600, 100, 3, 2, 8, 16, 64, "scalar", 8, 100, 100),
+    "l1_wide":     ("lattice", 400, 100, 2, 2, 32, 64, 100, "scalar", 32, 100, 50),
+    "dup":         ("dup", 380, 128, 2, 1, 16, 32, 160, "avx_fma", 16, 100, 0),
+    "dup_wide":    ("dup", 380, 128, 2, 1, 32, 64, 160, "avx_fma", 32, 100, 50),
+}
+_TIE_BUILT = {}
+
+
+def tie_inputs(name: str):
+    """(rows, ids, levels, group label per row or None) of a TIE_CASES entry"""
+    corpus, n, dim, nz, metric, m, m0, efc, kern, lm, _, _ = TIE_CASES[name]
+    if corpus == "dup":
+        data, label = duplicate_groups(2, [20, 80], n - 100, dim, 5)
+    else:
+        data, label = lattice_rows(n, dim, nz, 1, support=32 if corpus == "lattice32" else 0), None
+    ids = np.arange(n, dtype=np.uint64) * 2 + 3
+    return data, ids, draw_levels(n, lm, seed=n + 1), label
+
+
+def tie_oracle_factory(orc, name: str):
+    _, _, dim, _, metric, m, m0, efc, kern, _, _, _ = TIE_CASES[name]
+    k = {"avx_fma": orc.K_AVX_FMA, "scalar": orc.K_SCALAR}[kern]
+    return lambda: orc.Index(dim, metric, kernel=k, m=m, m0=m0, ef_construction=efc)
+
+
+def tie_case(orc, name: str):
+    """The oracle's sequential build of a TIE_CASES entry, once per process (nobody changes it): a dict with the oracle index `oix`, its
+    export `ex`, the inputs (`data`, `ids`, `levels`, `label`), `prone` (tie_prone_inserts), `full` (layer-0 rows with m0 ids) and
+    `unreachable` (unreachable_l0 of the oracle's own graph).  Asserts the counts the case is there for."""
+    if name not in _TIE_BUILT:
+        _, n, _, _, _, _, m0, efc, _, _, min_prone, min_full = TIE_CASES[name]
+        data, ids, lv, label = tie_inputs(name)
+        oix, prone = tie_prone_inserts(orc, tie_oracle_factory(orc, name), data, ids, lv, efc, TIE_BEAM)
+        ex = oix.export()
+        full = int((np.diff(ex["l0_offsets"].astype(np.int64)) == m0).sum())
+        unreach = unreachable_l0(ex)
+        print(f"oracle {name}: {prone} of {n} inserts tie-prone at a beam of {TIE_BEAM}, {full} layer-0 rows with {m0} ids, {unreach} unreachable nodes")
+        assert prone >= min_prone and full >= min_full, (name, prone, full)
+        _TIE_BUILT[name] = dict(oix=oix, ex=ex, data=data, ids=ids, levels=lv, label=label, prone=prone, full=full, unreachable=unreach)
+    return _TIE_BUILT[name]
