@@ -429,7 +429,7 @@ extern "C" int hvx_batcher_new_lanes(hvx_index *ix, const hvx_search_params *par
 // The prefiltered branch of the operator (execution/interpreter/access/search/storage.rs:140-163: `Some(candidates) =>
 // index.search_restricted(..)`): every caller brings its OWN candidate ids; a batch of them is ONE launch of the exact scan
 // (csrc/hvx_restricted_exact.hip).  The plan must answer such sets exactly: strategy EXACT, or AUTO with slots whose rows stay within the
-// device plan's limit; k <= 64.  Candidate lists longer than max_ids_per_query do not ride in a batch: the host calls
+// device plan's limit; k <= 800.  Candidate lists longer than max_ids_per_query do not ride in a batch: the host calls
 // hvx_search_restricted_batch_params for them (a list that long keeps the device busy by itself).
 extern "C" int hvx_batcher_new_restricted(hvx_index *ix, const hvx_restricted_params *params, uint32_t max_batch, uint32_t max_wait_us,
                                           uint32_t lanes, uint32_t max_ids_per_query, hvx_batcher **out) {
@@ -440,7 +440,8 @@ extern "C" int hvx_batcher_new_restricted(hvx_index *ix, const hvx_restricted_pa
     if (max_ids_per_query == 0) max_ids_per_query = 4096;
     if (max_ids_per_query > 1000000u) return fail(HVX_ERR_CANDIDATE_LIMIT, "restricted vector search accepts at most 1000000 unique candidates");
     if (!restricted_direct_supported(ix, params->k))
-        return fail(HVX_ERR_UNSUPPORTED, "the batched prefiltered search serves k <= 64 over f32 / bf16 rows of a non-empty image");
+        return fail(HVX_ERR_UNSUPPORTED, "the batched prefiltered search serves k <= 800 over f32 / bf16 rows of a non-empty image (k > 64: rows of at most "
+                    "9 712 floats at k > 256, 14 320 at k <= 256: the query row and the lists' hand-over share 64 KiB of LDS)");
     RestrictedPlan plan;
     int rc = restricted_make_plan(*params, max_ids_per_query, ix->dev.dim, &plan, ix);
     if (rc) return rc;

@@ -293,8 +293,17 @@ hipError_t launch_fp8_code_norm(const uint8_t *codes, uint32_t n, uint32_t dim, 
 int flat_scan_host(hvx_index *ix, const float *queries, uint32_t b, uint32_t k, const uint32_t *d_subset,
                    uint32_t n_rows, uint64_t *out_ids, float *out_scores, uint32_t *out_counts,
                    uint32_t *out_status, hvx_stats *stats);
-// the one-launch restricted exact scan (hvx_restricted_exact.hip): k <= 64 over f32 / bf16 rows of a non-empty image
+// the one-launch restricted exact scan (hvx_restricted_exact.hip): k <= 800 (MAX_RESTRICTED_RESULT_COUNT, restricted.rs:55) over f32 /
+// bf16 rows of a non-empty image
 bool restricted_direct_supported(const hvx_index *ix, uint32_t k);
+// whether `lists` candidate lists (the longest of `longest` ids) answered in one launch beat the older pipeline list by list; true at k <= 64
+bool restricted_direct_pays(const hvx_index *ix, uint32_t k, uint32_t lists, uint64_t longest);
+// whether the older exact pipeline answers a set at this k at all (over bf16 rows it stops at k 511 and serves six dimensions): a request
+// it refuses goes to the one-launch scan whatever the speed rule says
+bool restricted_older_serves(const hvx_index *ix, uint32_t k);
+// its builds with a result list of 4 / 13 registers per lane (hvx_restricted_wide4.hip / hvx_restricted_wide13.hip); args = the launch's argument block
+hipError_t restricted_direct_launch_wide4(const void *args, bool ext, bool unrolled, hipStream_t s);
+hipError_t restricted_direct_launch_wide13(const void *args, bool ext, bool unrolled, hipStream_t s);
 int restricted_direct_enqueue(hvx_index *ix, const float *d_queries, uint32_t b, uint32_t k, uint32_t k_stride, const uint32_t *d_rows,
                               uint32_t n_rows, const uint64_t *d_ext_ids, const uint64_t *d_offsets, uint32_t max_set, uint64_t *d_ids,
                               float *d_scores, uint32_t *d_counts, uint32_t *d_status, const uint32_t *d_lens = nullptr, uint32_t ext_stride = 0,

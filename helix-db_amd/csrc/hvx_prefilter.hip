@@ -1233,7 +1233,10 @@ static int prefilter_search_impl(const hvx_index *cix, const hvx_csr *cg, const 
     std::lock_guard<std::mutex> glock(g->mu);
     std::lock_guard<std::mutex> lock(ix->mu);
     ix->sync_rewrites();
-    if (mode == HVX_PREFILTER_EXPAND && direction <= HVX_DIR_BOTH && ix->opt[HVX_OPT_RESTRICTED_DIRECT] != 1u && !rp.explicit_budgets && k <= 64u &&
+    if (mode == HVX_PREFILTER_EXPAND && direction <= HVX_DIR_BOTH && ix->opt[HVX_OPT_RESTRICTED_DIRECT] != 1u && !rp.explicit_budgets &&
+        // (k > 64: one query per tile over the shared set -- that shape lost to the pipeline at 10 000 ids, and the hop in front of it has not
+        // been measured: the lean route takes it when forced or when the pipeline would refuse)
+        (k <= 64u || ix->opt[HVX_OPT_RESTRICTED_DIRECT] == 2u || !restricted_older_serves(ix, k)) &&
         restricted_direct_supported(ix, k) && ix->dev.n != 0u) {
         // what one hop can reach at most: seeds x the largest adjacency row (both rows for direction Both), never more than the graph
         const uint64_t per_seed = (direction != HVX_DIR_IN ? g->max_out_deg : 0) + (direction != HVX_DIR_OUT ? g->max_in_deg : 0);

@@ -591,6 +591,9 @@ int walk_shared_set(hvx_index *ix, const float *queries, uint32_t b, uint32_t k_
 bool use_direct(const hvx_index *ix, uint32_t b, uint32_t k, uint32_t n_rows) {
     if (ix->opt[HVX_OPT_RESTRICTED_DIRECT] == 1u || n_rows == 0 || !restricted_direct_supported(ix, k)) return false;
     if (ix->opt[HVX_OPT_RESTRICTED_DIRECT] == 2u) return true;
+    // a shared set at k > 64 is scanned once per query by the wide builds (one query per tile): measured at 10 000 ids x 1536 they lose to
+    // the matrix-core pipeline for 4 and for 32 queries at k 100, 256 and 800 (0.69 - 3.4 ms against 0.49 - 1.06: profiles/restricted_wide_ab.log)
+    if (k > 64u) return !restricted_older_serves(ix, k); // (what the pipeline refuses -- bf16 rows at k > 511 or an odd dimension -- is served here)
     const uint64_t work = (uint64_t)b * n_rows * ix->dev.dim;
     return work <= (1ull << 26) || (work <= (1ull << 31) && !flat_scan_on_matrix_cores(ix, b, k, n_rows));
 }
@@ -763,8 +766,8 @@ int restricted_set(hvx_index *ix, const float *queries, uint32_t b, const hvx_re
     // ONE query with its candidate ids (the operator's call, storage.rs:140-163) under a plan that is exact for a list this long: the
     // one-launch scan maps, dedupes and scans the ids on the device -- no host-side sort / unique / id -> row pass (round 6: those and two
     // staged copies were ~90 us of a 145-us call at 10 000 ids)
-    if (b == 1 && n_allowed != 0 && n_allowed <= 1000000ull && rp.k <= 64u && !rp.explicit_budgets && ix->opt[HVX_OPT_RESTRICTED_DIRECT] != 1u &&
-        restricted_direct_supported(ix, rp.k) && (n_allowed * (uint64_t)ix->dev.dim <= (1ull << 28) || ix->opt[HVX_OPT_RESTRICTED_DIRECT] == 2u)) {
+    if (b == 1 && n_allowed != 0 && n_allowed <= 1000000ull && !rp.explicit_budgets && ix->opt[HVX_OPT_RESTRICTED_DIRECT] != 1u &&
+        restricted_direct_supported(ix, rp.k) && restricted_direct_pays(ix, rp.k, 1, n_allowed) && (n_allowed * (uint64_t)ix->dev.dim <= (1ull << 28) || ix->opt[HVX_OPT_RESTRICTED_DIRECT] == 2u)) {
         HostPlan hp1;
         if (make_plan(rp, n_allowed, ix->dev.dim, &hp1, ix) == HVX_OK && hp1.strategy == HVX_RESTRICTED_EXACT) {
             const uint64_t offs[2] = {0, n_allowed};
@@ -896,7 +899,8 @@ int hvx::restricted_search_host(hvx_index *ix, const float *queries, uint32_t b,
         return restricted_set(ix, queries, b, rp, allowed_ids, n_allowed, out_ids, out_scores, out_counts, out_status, out_rstats, stats);
     // One candidate list per query (the operator's shape: storage.rs:140-163).  Lists that the plan answers exactly -- all of them under
     // the device plan, up to a GiB of rows each -- are scanned in ONE launch for the whole batch (round 6); anything else list by list.
-    bool batched = rp.k <= 64u && restricted_direct_supported(ix, rp.k) && ix->opt[HVX_OPT_RESTRICTED_DIRECT] != 1u && !rp.explicit_budgets;
+    bool batched = restricted_direct_supported(ix, rp.k) && ix->opt[HVX_OPT_RESTRICTED_DIRECT] != 1u && !rp.explicit_budgets &&
+                   restricted_direct_pays(ix, rp.k, b, 0); // (fewer lists than pay together: list by list, each by the single-list rule)
     for (uint32_t q = 0; q < b && batched; ++q) {
         const uint64_t len = allowed_offsets[q + 1] - allowed_offsets[q];
         if (len == 0) continue;

@@ -918,6 +918,14 @@ class ValidatedVectorReadIndex:
             d_counts.data_ptr(), d_status.data_ptr(), C.byref(stats) if want_stats else None))
         return stats.as_dict() if want_stats else None
 
+    def search_restricted_lists_device(self, d_queries, k, d_ids, stride, d_lens, max_len, d_out_ids, d_out_scores, d_out_counts, d_out_status=None):
+        """hvx_search_restricted_lists_device: device-resident queries [b][dim], query q with its own candidate ids d_ids[q * stride .. +
+        d_lens[q]) (u64 external ids, any order, duplicates allowed, unknown ids skipped); exact strategy, k <= 800, ONE launch on the
+        index's stream, nothing synchronised (sync() before the outputs are read)."""
+        _check(lib().hvx_search_restricted_lists_device(
+            self._h, d_queries.data_ptr(), d_queries.shape[0], k, d_ids.data_ptr(), stride, d_lens.data_ptr(), max_len,
+            d_out_ids.data_ptr(), d_out_scores.data_ptr(), d_out_counts.data_ptr(), None if d_out_status is None else d_out_status.data_ptr()))
+
     def merge_topk_device(self, g, b, k, d_ids, d_scores, d_counts, d_out_ids, d_out_scores, d_out_counts):
         _check(lib().hvx_merge_topk_device(self._h, g, b, k, d_ids.data_ptr(), d_scores.data_ptr(), d_counts.data_ptr(),
                                            d_out_ids.data_ptr(), d_out_scores.data_ptr(), d_out_counts.data_ptr()))

@@ -157,7 +157,7 @@ enum hvx_option {
                                         2 = always where it is built, 3 = always, with ONE gatherer even where three are built */
     HVX_OPT_DELETE_SEQUENTIAL = 10,  /* 0: one fused launch per relinked row (round 6); 1: every source in the one-wavefront kernel; 2: as 0 (it chose
                                         two launches per row, since retired) -- both produce the reference's rows */
-    HVX_OPT_RESTRICTED_DIRECT = 11,  /* restricted exact scans of k <= 64: 0 = the one-launch reference-order kernel (csrc/hvx_restricted_exact.hip) where it is
+    HVX_OPT_RESTRICTED_DIRECT = 11,  /* restricted exact scans of k <= 800 (MAX_RESTRICTED_RESULT_COUNT, restricted.rs:55): 0 = the one-launch reference-order kernel (csrc/hvx_restricted_exact.hip) where it is
                                         the cheaper one (b x candidates x dim <= 2^31), 1 = never, 2 = always */
     HVX_OPT_RESTRICTED_EXACT_MIB = 12, /* device plan of HVX_RESTRICTED_AUTO: candidate sets whose rows take at most this many MiB are scanned
                                         exactly; 0 = 1024 */
@@ -375,8 +375,9 @@ int hvx_search_restricted_batch_params(const hvx_index *, const float *queries, 
 /* Device-resident surface of the prefiltered branch, exact strategy (csrc/hvx_restricted_exact.hip): b queries in HBM, query q with its OWN
  * candidate ids d_allowed_ids[q * stride .. + d_lens[q]) -- external ids in any order; duplicates count once (RestrictedVectorCandidates is a
  * set, restricted.rs:303-371), ids that hold no (live) vector are skipped (:615-659), an empty list answers with nothing and status 0 before
- * the query is validated (:539-541).  k <= 64, f32 / bf16 rows.  ONE launch for the batch; nothing is synchronised; outputs may be HBM or
- * mapped host rows.  max_len = the longest list (<= stride). */
+ * the query is validated (:539-541).  k <= 800 (MAX_RESTRICTED_RESULT_COUNT, restricted.rs:55), f32 / bf16 rows.  At k > 64 a row holds at
+ * most 14 320 floats (k <= 256) / 9 712 floats (k > 256): HVX_ERR_UNSUPPORTED beyond, here and in hvx_batcher_new_restricted.  ONE launch
+ * for the batch; nothing is synchronised; outputs may be HBM or mapped host rows.  max_len = the longest list (<= stride). */
 int hvx_search_restricted_lists_device(const hvx_index *, const float *d_queries, uint32_t b, uint32_t k, const uint64_t *d_allowed_ids,
                                        uint32_t stride, const uint32_t *d_lens, uint32_t max_len, uint64_t *d_out_ids /*[b][k]*/,
                                        float *d_out_scores, uint32_t *d_out_counts, uint32_t *d_out_status /*nullable*/);
@@ -573,7 +574,7 @@ int hvx_batcher_eventfd(hvx_batcher *); /* -1 on failure */
 /* The operator's OTHER branch (execution/interpreter/access/search/storage.rs:140-163: `Some(candidates) => index.search_restricted(..)`):
  * every caller brings its own candidate ids (a where_() / traversal filter evaluated by the host).  A batch of such callers is ONE launch of
  * the exact scan with per-query candidate lists -- 256 callers x 1 000 ids x 1536 floats: 0.26 ms of device time (profiles/r06d_*).
- * params: k <= 64; the plan must answer a max_ids_per_query-id set exactly (strategy EXACT, or AUTO within the device plan's limit); lists
+ * params: k <= 800 (MAX_RESTRICTED_RESULT_COUNT, restricted.rs:55); the plan must answer a max_ids_per_query-id set exactly (strategy EXACT, or AUTO within the device plan's limit); lists
  * beyond max_ids_per_query (0 = 4 096; pinned memory: lanes + 2 buffers x max_batch x max_ids_per_query x 8 B) are refused with
  * HVX_ERR_UNSUPPORTED -- the host sends those through hvx_search_restricted_batch_params.  Tickets of a restricted batcher are polled /
  * waited for / awaited through the eventfd like any other; hvx_batcher_search / _submit refuse a restricted batcher and vice versa. */
