@@ -730,3 +730,192 @@ def tie_case(orc, name: str):
         assert prone >= min_prone and full >= min_full, (name, prone, full)
         _TIE_BUILT[name] = dict(oix=oix, ex=ex, data=data, ids=ids, levels=lv, label=label, prone=prone, full=full, unreachable=unreach)
     return _TIE_BUILT[name]
+
+
+# ---- the graph prefilter at sizes where its kernels split their work (tests/test_prefilter_fixtures.py proves on the CPU that
+# ---- every case below is what tests/test_gpu_prefilter_scale.py says it is)
+BITMAP_BLOCK_IDS = 8192   # bitmap_count / _compact / _select cut the candidate bitmap into blocks of 256 words
+UNBOUNDED = 1 << 30       # a max_depth no traversal here reaches
+
+
+def csr_graph(n: int, seed: int, avg_row: int = 3, hubs=(), rows=None, sinks=(), n_labels: int = 0):
+    """A seeded CSR graph in the reference's form (crates/graph-algorithms/src/model.rs:656-666: every outgoing row ascends by
+    target); parallel edges and self-loops occur.  Row lengths are uniform in 0 .. 2 * avg_row, targets uniform over the nodes.
+    `hubs` = (node, row length) overrides, `rows` = {node: the row's targets} spelled out, `sinks` = (node, k): k different
+    ordinary sources trade one of their arcs for one to `node`.  Returns (offsets u64 [n + 1], targets u64, labels u32 or None)."""
+    rng = np.random.default_rng(seed)
+    rows = {int(u): np.sort(np.asarray(r, np.int64)) for u, r in (rows or {}).items()}
+    lens = rng.integers(0, 2 * avg_row + 1, n)
+    for u, length in hubs:
+        lens[u] = length
+    for u, r in rows.items():
+        lens[u] = r.size
+    off = np.zeros(n + 1, np.int64)
+    off[1:] = np.cumsum(lens)
+    tgt = rng.integers(0, n, int(off[-1]))
+    for u, r in rows.items():
+        tgt[off[u]:off[u + 1]] = r
+    ordinary = np.ones(n, bool)
+    ordinary[[u for u, _ in hubs] + list(rows)] = False
+    ordinary &= lens > 0
+    for v, k in sinks:
+        src = rng.choice(np.nonzero(ordinary)[0], k, replace=False)
+        tgt[off[src]] = v
+    owner = np.repeat(np.arange(n), lens)
+    tgt = tgt[np.lexsort((tgt, owner))]
+    lab = rng.integers(0, n_labels, tgt.size).astype(np.uint32) if n_labels else None
+    return off.astype(np.uint64), tgt.astype(np.uint64), lab
+
+
+def chain_graph(length: int):
+    """0 -> 1 -> ... -> length: (n, offsets, targets)"""
+    n = length + 1
+    off = np.minimum(np.arange(n + 1), length).astype(np.uint64)
+    return n, off, np.arange(1, n, dtype=np.uint64)
+
+
+def bitmap_ids(words) -> set:
+    """the ids whose bit is set in a candidate bitmap (u64 or u32 words, bit i of word w = id 64 w + i / 32 w + i)"""
+    return set(np.nonzero(np.unpackbits(np.ascontiguousarray(words).view(np.uint8), bitorder="little"))[0].tolist())
+
+
+def bitmap_blocks(ids) -> list:
+    """the bitmap blocks (of BITMAP_BLOCK_IDS ids) that hold at least one of `ids`, ascending"""
+    return sorted(set(int(i) // BITMAP_BLOCK_IDS for i in ids))
+
+
+def has_empty_block_between(ids) -> bool:
+    blocks = bitmap_blocks(ids)
+    return any(b - a > 1 for a, b in zip(blocks, blocks[1:]))
+
+
+def row_union(off, tgt, seeds, lab=None, allowed=(), direction: int = 0) -> np.ndarray:
+    """what one `expand` hop from `seeds` reaches (access/expand.rs:16-80): the union of their rows, ascending (numpy only)"""
+    off = np.asarray(off, np.int64)
+    tgt = np.asarray(tgt, np.int64)
+    keep = np.ones(tgt.size, bool) if lab is None or not len(allowed) else np.isin(lab, np.asarray(allowed))
+    owner = np.repeat(np.arange(off.size - 1), np.diff(off))
+    is_seed = np.zeros(off.size - 1, bool)
+    is_seed[np.asarray(seeds, np.int64)] = True
+    parts = []
+    if direction in (0, 2):
+        parts.append(tgt[keep & is_seed[owner]])
+    if direction in (1, 2):
+        parts.append(owner[keep & is_seed[tgt]])
+    return np.unique(np.concatenate(parts)).astype(np.uint64)
+
+
+# the 20 011-node graph of the traversal tests (not a multiple of 32: the last bitmap word is partial): two hubs and one node
+# with a long INCOMING row, three labels
+G20K = dict(n=20011, seed=20011, hubs=((5, 300), (12345, 1000)), sinks=((777, 200),), n_labels=3)
+G20K_HUBS, G20K_SINK = (5, 12345), 777
+# the 70 001-node graph of the fused-hop tests.  1000 .. 1063 is one wavefront's group of seeds with rows of length 0, 1, 16, 17,
+# 65 and 1 000 among ordinary ones; 2000 reaches every id of CONTIGUOUS_IDS; 2001 only ids that hold no vector in either image;
+# 2002 is 300 parallel edges to five nodes; 300 .. 303 and the rows of what they reach are an island whose two-hop neighbourhood
+# has candidates on both sides of two block boundaries and leaves blocks 4 and 5 empty; 304 / 305 are two populous rows inside
+# blocks 0 and 6; 3000 has a long incoming row
+G70K_GROUP = ((1003, 0), (1010, 1), (1020, 16), (1021, 17), (1030, 65), (1040, 1000))
+THIRD_IDS = np.arange(0, 70001, 3, dtype=np.uint64)           # 23 334 rows behind the binary-search id map
+CONTIGUOUS_IDS = np.arange(5000, 30000, dtype=np.uint64)
+VECTORLESS = (1, 4, 7, 40003, 60001)
+ISLAND_SEEDS = (300, 301, 302, 303)
+_ISLAND = {300: [8191, 8192], 301: [24575, 24576], 302: [10, 8000], 303: [49152, 50001, 57343],
+           8191: [8190, 8192], 8192: [8193], 24575: [24570], 24576: [24580], 10: [11], 8000: [], 49152: [49153], 50001: [57343],
+           57343: [57342]}
+
+
+def _g70k_rows():
+    rng = np.random.default_rng(70001)
+    rows = dict(_ISLAND)
+    rows[304] = rng.choice(np.arange(0, 8192), 200, replace=False)
+    rows[305] = rng.choice(np.arange(49152, 57344), 200, replace=False)
+    rows[2000] = CONTIGUOUS_IDS
+    rows[2001] = VECTORLESS
+    rows[2002] = np.repeat([9, 12, 6000, 6003, 6006], 60)
+    return rows
+
+
+_GRAPHS = {}
+
+
+def prefilter_graph(name: str):
+    """(n, offsets, targets, labels) of "g20k" / "g70k", built once per process; nobody changes the arrays"""
+    if name not in _GRAPHS:
+        if name == "g20k":
+            _GRAPHS[name] = (G20K["n"],) + csr_graph(**G20K)
+        else:
+            _GRAPHS[name] = (70001,) + csr_graph(70001, seed=70001, hubs=G70K_GROUP, rows=_g70k_rows(), sinks=((3000, 200),), n_labels=3)
+    return _GRAPHS[name]
+
+
+def _many_seeds(n: int, distinct: int, repeats: int, seed: int, first=()):
+    """`distinct` different nodes and `repeats` second copies of some of them, shuffled, behind the nodes of `first`"""
+    rng = np.random.default_rng(seed)
+    pick = rng.choice(n, distinct, replace=False)
+    s = np.concatenate([pick, rng.choice(pick, repeats)])
+    rng.shuffle(s)
+    return np.concatenate([np.asarray(first, np.int64), s]).astype(np.uint64)
+
+
+def prefilter_traversals():
+    """name -> (graph, seeds, max_depth, direction, allowed labels, hub degree): the traversals the scale tests run"""
+    n = G20K["n"]
+    return {
+        "out1": ("g20k", np.array([2], np.uint64), UNBOUNDED, 0, (), 0),
+        "in1": ("g20k", np.array([2], np.uint64), UNBOUNDED, 1, (), 0),
+        "both1": ("g20k", np.array([2], np.uint64), UNBOUNDED, 2, (), 0),
+        "many": ("g20k", _many_seeds(n, 4600, 400, 1), 3, 0, (), 0),                      # 5 000 seeds, shuffled, 400 twice
+        "twice": ("g20k", np.tile(np.arange(n, dtype=np.uint64), 2), 2, 2, (), 0),        # more seeds than nodes
+        "labelled": ("g20k", _many_seeds(n, 1400, 98, 2, first=G20K_HUBS), 3, 2, (1, 2), 0),   # 1 500 seeds, both hubs first
+        "hubs": ("g20k", np.array([G20K_HUBS[1], 7], np.uint64), UNBOUNDED, 0, (), 100),  # one hub a seed, the other one met
+        "island": ("g70k", np.array(ISLAND_SEEDS, np.uint64), 2, 0, (), 0),
+        "dense": ("g70k", np.arange(0, 3000, dtype=np.uint64), 2, 0, (), 0),
+    }
+
+
+_ORACLE_RUNS = {}
+
+
+def prefilter_oracle(orc, name: str):
+    """orc.breadth_first of a prefilter_traversals() entry, once per process: (visits, edges)"""
+    if name not in _ORACLE_RUNS:
+        graph, seeds, md, direction, allowed, hub = prefilter_traversals()[name]
+        n, off, tgt, lab = prefilter_graph(graph)
+        _ORACLE_RUNS[name] = orc.breadth_first(n, off.astype(np.int64), tgt, lab, seeds, md, direction, allowed, hub)
+    return _ORACLE_RUNS[name]
+
+
+def hop_cases():
+    """name -> (seeds, keyword arguments of prefilter_search_batch) on "g70k": the one-hop cases of the fused call"""
+    group = np.arange(1000, 1064, dtype=np.uint64)
+    run = lambda c: np.arange(1000, 1000 + c, dtype=np.uint64)
+    return {
+        "one": (run(1), {}), "group": (group, {}), "65": (run(65), {}), "1024": (run(1024), {}), "1025": (run(1025), {}),
+        "5000": (run(5000), {}),                                                   # the seed buffer regrows; bound > both images
+        "duplicates": (np.concatenate([group, group, np.full(5, 1040, np.uint64)]), {}),
+        "parallel": (np.array([2002], np.uint64), {}),
+        "in": (np.concatenate([group, np.array([3000], np.uint64)]), dict(direction=1)),
+        "both_labelled": (run(700), dict(direction=2, allowed_labels=[1])),
+        "every_row": (np.array([2000, 1040], np.uint64), {}),                      # reaches every row of the contiguous image
+        "vectorless": (np.array([2001], np.uint64), {}),
+        "sparse": (np.arange(300, 306, dtype=np.uint64), {}),                      # blocks 0 - 3 and 6, boundary ids
+    }
+
+
+# the sampled walk's image: walk_harness.random_graph(.., WALK_ROWS, 32, L2SQ, .., id_gap=True) holds ids 1, 4, .. 16 798, so the graph
+# around it has three bitmap blocks (9 000 rows, four blocks, cost 10 s of oracle inserts; 5 600 is the smallest round count whose
+# ids reach well into the third block)
+WALK_ROWS = 5600
+WALK_NODES = 3 * (WALK_ROWS - 1) + 1 + 3
+
+
+def walk_hop_graph(n_nodes: int, seed: int, sources: int = 1500):
+    """One edge per source (config #3's where_() shape) whose targets lie in the first and the last bitmap block only, the ids on
+    the block edges among them: (offsets, targets, the sources)"""
+    rng = np.random.default_rng(seed)
+    last = (n_nodes - 1) // BITMAP_BLOCK_IDS * BITMAP_BLOCK_IDS
+    pool = np.concatenate([np.arange(1, BITMAP_BLOCK_IDS), np.arange(last, n_nodes)])
+    edge_ids = np.array([BITMAP_BLOCK_IDS - 2, BITMAP_BLOCK_IDS - 1, last, last + 1], np.int64)
+    tgt = np.concatenate([edge_ids, rng.choice(pool, sources - edge_ids.size)]).astype(np.uint64)
+    off = np.minimum(np.arange(n_nodes + 1), sources).astype(np.uint64)
+    return off, tgt, np.arange(sources, dtype=np.uint64)
