@@ -52,6 +52,12 @@ struct hvx_csr {
     size_t cap_h_seeds = 0;
     hipEvent_t done = nullptr;                      // recorded behind a traversal whose consumer runs on another stream (fused prefilter search)
     uint64_t max_out_deg = 0, max_in_deg = 0;       // largest row of either adjacency: bounds what one hop from s seeds can reach (round 6)
+    // chains of expand hops (hvx_expand_path_filter / hvx_prefilter_path_search_batch_params), allocated on first use
+    uint32_t *visited2 = nullptr;                   // [words] the second frontier bitmap: the hops ping-pong between it and `visited`
+    uint32_t *hop_cnt = nullptr;                    // [16] per hop: bits set in its target bitmap
+    uint32_t *mask_dev = nullptr;                   // [words] the Filter step's node mask
+    uint32_t *h_mask = nullptr;                     // pinned staging of the mask
+    uint32_t *h_hops = nullptr;                     // pinned [16]: the hop sizes read back
 };
 
 namespace {
@@ -152,6 +158,8 @@ void csr_free(hvx_csr *g) {
     (void)hipSetDevice(g->device);
     for (void *p : g->allocs) (void)hipFree(p);
     if (g->h_seeds) (void)hipHostFree(g->h_seeds);
+    if (g->h_mask) (void)hipHostFree(g->h_mask);
+    if (g->h_hops) (void)hipHostFree(g->h_hops);
     if (g->done) (void)hipEventDestroy(g->done);
     if (g->stream) (void)hipStreamDestroy(g->stream);
     delete g;
@@ -238,13 +246,13 @@ extern "C" int hvx_csr_import(uint64_t n_nodes, uint64_t n_edges, const uint64_t
     return HVX_OK;
 }
 
-static int upload_labels(hvx_csr *g, const uint32_t *labels, uint32_t n) {
+static int upload_labels(hvx_csr *g, const uint32_t *labels, uint32_t n, hipStream_t s = nullptr) {
     if (n > g->labels_cap) {
         int rc = csr_alloc(g, (void **)&g->labels, (size_t)n * 4);
         if (rc) return rc;
         g->labels_cap = n;
     }
-    if (n) HIP_TRY(hipMemcpyAsync(g->labels, labels, (size_t)n * 4, hipMemcpyHostToDevice, g->stream));
+    if (n) HIP_TRY(hipMemcpyAsync(g->labels, labels, (size_t)n * 4, hipMemcpyHostToDevice, s ? s : g->stream));
     return HVX_OK;
 }
 
@@ -1122,6 +1130,159 @@ __global__ __launch_bounds__(1024) void expand_collect_kernel(CsrView g, const u
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// A chain of `expand` hops (hvx_expand_path_filter / hvx_prefilter_path_search_batch_params): hop i's frontier is the bitmap hop i - 1
+// wrote, so no frontier crosses PCIe and the host never learns a frontier's size between two hops.  Kernel boundaries order the hops.
+// ---------------------------------------------------------------------------------------------
+struct PathHopArgs {
+    CsrView g;
+    const uint32_t *front;   // hop 0: the seed list (pinned host memory), n_front entries; hops >= 1: the bitmap of the frontier,
+    uint32_t n_front;        // n_front = the graph's node count
+    uint32_t direction;
+    const uint32_t *allowed; // this hop's allow-set
+    uint32_t n_allowed;
+    uint32_t *dst;           // the bitmap of the next frontier (cleared on the stream before the launch)
+    uint32_t *hop_size;      // += bits this launch set in dst: |F(i + 1)|
+    // the last hop of the lean route only (kCollect): rows of the fresh nodes that pass the mask and hold a live vector -> rows_out,
+    // counters[0] = rows of the list, counters[1] = candidate population (fresh AND mask), as expand_collect_kernel leaves them
+    const uint32_t *mask;    // nullable
+    const uint64_t *ids;
+    uint32_t n, contiguous;
+    const uint32_t *dead;
+    uint32_t *rows_out;
+    uint32_t rows_cap;
+    uint32_t *counters;
+};
+
+// One hop.  kBitmap: a wavefront takes 64 consecutive node numbers (two words of the frontier's bitmap), one node per lane where the bit
+// is set; otherwise 64 entries of the seed list.  The row work is split as in expand_collect_kernel: rows of at most 16 arcs by their
+// own lane, longer ones by the whole wavefront, one at a time.  What a thread sets in dst it counts in a register: the hop's size (and
+// the population) cost ONE update per workgroup, at its end.  Only the row list needs a position per step (kCollect): there the light
+// rows are walked in lock step across the workgroup and share one update of counters[0] per step.
+template <bool kBitmap, bool kCollect>
+__global__ __launch_bounds__(1024) void path_hop_kernel(PathHopArgs a) {
+    const int lane = (int)(threadIdx.x & 63u);
+    const uint32_t wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
+    constexpr uint32_t kLight = 16;
+    __shared__ uint32_t s_r[16], s_base, s_steps, s_fresh, s_pop;
+    uint32_t n_fresh = 0, n_pop = 0;
+    // one arc: test-and-set its target in dst; kCollect: the row of a fresh target that passes the mask (kSentinel otherwise)
+    auto visit = [&](bool active, const uint32_t *tgt, const uint32_t *lab, uint64_t at) __attribute__((always_inline)) -> uint32_t {
+        uint32_t row = kSentinel;
+        if (active && (!lab || label_ok(lab[at], a.allowed, a.n_allowed))) {
+            const uint32_t v = tgt[at];
+            const uint32_t bit = 1u << (v & 31u);
+            if ((atomicOr(&a.dst[v >> 5], bit) & bit) == 0u) {
+                ++n_fresh;
+                if (kCollect && (!a.mask || (a.mask[v >> 5] & bit))) {
+                    ++n_pop;
+                    row = find_row(a.ids, a.n, (uint64_t)v, a.contiguous != 0u, a.dead);
+                }
+            }
+        }
+        return row;
+    };
+    for (uint32_t c0 = blockIdx.x * blockDim.x; c0 < a.n_front; c0 += gridDim.x * blockDim.x) {
+        const uint32_t s0 = c0 + wave * 64u;
+        bool have;
+        uint32_t node;
+        if (kBitmap) {
+            // (the bitmap holds whole pairs of words: s0 < n_front keeps the read inside it, and a set bit is a node of the graph)
+            const uint32_t word = s0 < a.n_front ? a.front[(s0 >> 5) + ((uint32_t)lane >> 5)] : 0u;
+            have = ((word >> ((uint32_t)lane & 31u)) & 1u) != 0u;
+            node = s0 + (uint32_t)lane;
+        } else {
+            have = s0 + (uint32_t)lane < a.n_front;
+            node = have ? a.front[s0 + (uint32_t)lane] : 0u;
+        }
+        for (int pass = 0; pass < 2; ++pass) {
+            const bool use_out = pass == 0;
+            if (use_out && a.direction == 1u) continue;  // In only
+            if (!use_out && a.direction == 0u) continue; // Out only
+            const uint64_t *off = use_out ? a.g.out_off : a.g.in_off;
+            const uint32_t *tgt = use_out ? a.g.out_tgt : a.g.in_tgt;
+            const uint32_t *lab = use_out ? a.g.out_lab : a.g.in_lab;
+            const uint64_t a0 = have ? off[node] : 0ull, a1 = have ? off[node + 1] : 0ull;
+            const uint32_t deg = (uint32_t)((a1 - a0) < 0xFFFFFFFFull ? (a1 - a0) : 0xFFFFFFFFull);
+            const bool light = deg <= kLight;
+            uint32_t steps = light ? deg : 0u;
+#pragma unroll
+            for (int sh = 32; sh > 0; sh >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)steps, sh, 64); steps = o > steps ? o : steps; }
+            if (kCollect) {
+                if (threadIdx.x == 0) s_steps = 0u;
+                __syncthreads();
+                if (lane == 0 && steps) atomicMax(&s_steps, steps);
+                __syncthreads();
+                const uint32_t wg_steps = s_steps;
+                for (uint32_t i = 0; i < wg_steps; ++i) {
+                    const uint32_t row = visit(light && i < deg, tgt, lab, a0 + i);
+                    const unsigned long long rm = __ballot(row != kSentinel);
+                    if (lane == 0) s_r[wave] = (uint32_t)__builtin_popcountll(rm);
+                    __syncthreads();
+                    if (threadIdx.x == 0) {
+                        uint32_t tr = 0;
+                        for (uint32_t w = 0; w < waves; ++w) tr += s_r[w];
+                        s_base = tr ? atomicAdd(&a.counters[0], tr) : 0u;
+                    }
+                    __syncthreads();
+                    if (row != kSentinel) {
+                        uint32_t pos = s_base + (uint32_t)__builtin_popcountll(rm & ((1ull << lane) - 1ull));
+                        for (uint32_t w = 0; w < wave; ++w) pos += s_r[w];
+                        if (pos < a.rows_cap) a.rows_out[pos] = row;
+                    }
+                    __syncthreads(); // (the next step writes s_r again)
+                }
+            } else {
+                for (uint32_t i = 0; i < steps; ++i) (void)visit(light && i < deg, tgt, lab, a0 + i);
+            }
+            unsigned long long heavy = __ballot(have && !light); // long rows: the whole wavefront strides over the arcs of one node at a time
+            while (heavy) {
+                const int l = __builtin_ctzll(heavy);
+                heavy &= heavy - 1ull;
+                const uint64_t h0 = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(a0 >> 32), l) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)a0, l);
+                const uint32_t hdeg = (uint32_t)__builtin_amdgcn_readlane((int)deg, l);
+                for (uint32_t j = 0; j < hdeg; j += 64u) {
+                    const uint32_t row = visit(j + (uint32_t)lane < hdeg, tgt, lab, h0 + j + (uint32_t)lane);
+                    if (kCollect) {
+                        const unsigned long long rm = __ballot(row != kSentinel);
+                        if (rm == 0ull) continue;
+                        uint32_t base = 0;
+                        if (lane == 0) base = atomicAdd(&a.counters[0], (uint32_t)__builtin_popcountll(rm));
+                        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+                        if (row != kSentinel) {
+                            const uint32_t pos = base + (uint32_t)__builtin_popcountll(rm & ((1ull << lane) - 1ull));
+                            if (pos < a.rows_cap) a.rows_out[pos] = row;
+                        }
+                    }
+                }
+            }
+        }
+    }
+    // the workgroup's share of the hop's size (and of the population): one update each
+#pragma unroll
+    for (int sh = 32; sh > 0; sh >>= 1) {
+        n_fresh += (uint32_t)__shfl_xor((int)n_fresh, sh, 64);
+        if (kCollect) n_pop += (uint32_t)__shfl_xor((int)n_pop, sh, 64);
+    }
+    if (threadIdx.x == 0) { s_fresh = 0u; s_pop = 0u; }
+    __syncthreads();
+    if (lane == 0) {
+        if (n_fresh) atomicAdd(&s_fresh, n_fresh);
+        if (kCollect && n_pop) atomicAdd(&s_pop, n_pop);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (s_fresh) atomicAdd(a.hop_size, s_fresh);
+        if (kCollect && s_pop) atomicAdd(&a.counters[1], s_pop);
+    }
+}
+
+// the Filter step on the bitmap route: final frontier AND node mask
+__global__ __launch_bounds__(256) void bitmap_and_kernel(uint32_t *bitmap, const uint32_t *mask, uint32_t n_words) {
+    const uint32_t w = blockIdx.x * 256u + threadIdx.x;
+    if (w < n_words) bitmap[w] &= mask[w];
+}
+
 } // namespace
 
 static int prefilter_search_impl(const hvx_index *cix, const hvx_csr *cg, const float *queries, uint32_t b, const hvx_restricted_params &rp,
@@ -1129,6 +1290,10 @@ static int prefilter_search_impl(const hvx_index *cix, const hvx_csr *cg, const 
                                  const uint32_t *allowed_label_ids, uint32_t n_labels, uint32_t hub_degree, uint32_t include_seeds,
                                  uint64_t *out_ids, float *out_scores, uint32_t *out_counts, uint32_t *out_status, uint64_t *out_candidates,
                                  hvx_restricted_stats *rstats, hvx_stats *stats);
+
+static int prefilter_bitmap_route(hvx_index *ix, hvx_csr *g, const uint32_t *bitmap, const float *queries, uint32_t b, const hvx_restricted_params &rp,
+                                  uint64_t *out_ids, float *out_scores, uint32_t *out_counts, uint32_t *out_status, uint64_t *out_candidates,
+                                  hvx_restricted_stats *rstats, hvx_stats *stats);
 
 // One hop + exact scan with ONE host wait (round 6; the reference issues one query per call, index_lifecycle_scale.rs:1893-1912: the
 // latency of this call is what a request sees).  Taken when the plan is exact WHATEVER the hop reaches -- strategy EXACT, or a planned
@@ -1254,6 +1419,15 @@ static int prefilter_search_impl(const hvx_index *cix, const hvx_csr *cg, const 
                             mode == HVX_PREFILTER_EXPAND ? 0u : hub_degree, mode == HVX_PREFILTER_EXPAND ? 0u : include_seeds,
                             mode == HVX_PREFILTER_EXPAND, nullptr, nullptr, ix->stream);
     if (rc) return rc; // (the index's stream waits for the traversal: the bitmap is complete before anything below reads it)
+    return prefilter_bitmap_route(ix, g, g->visited, queries, b, rp, out_ids, out_scores, out_counts, out_status, out_candidates, rstats, stats);
+}
+
+// The bitmap route of the fused calls: `bitmap` (a candidate bitmap of g, complete on ix->stream) -> count / scan / compact -> the plan.
+static int prefilter_bitmap_route(hvx_index *ix, hvx_csr *g, const uint32_t *bitmap, const float *queries, uint32_t b, const hvx_restricted_params &rp,
+                                  uint64_t *out_ids, float *out_scores, uint32_t *out_counts, uint32_t *out_status, uint64_t *out_candidates,
+                                  hvx_restricted_stats *rstats, hvx_stats *stats) {
+    const uint32_t k = rp.k;
+    int rc;
     const uint32_t n_words = ((g->n + 63u) / 64u) * 2u, n_blocks = (n_words + 255u) / 256u;
     if (2 * (n_blocks + 2) > ix->cap_pf_blocks) {
         if ((rc = ix->regrow((void **)&ix->pf_blocks, (size_t)2 * (n_blocks + 2) * 4))) return rc;
@@ -1262,7 +1436,7 @@ static int prefilter_search_impl(const hvx_index *cix, const hvx_csr *cg, const 
     uint32_t *d_total_bits = ix->pf_blocks + n_blocks + 1;
     uint32_t *d_block_bits = ix->pf_blocks + n_blocks + 2; // [n_blocks + 1]: per-block candidate counts, then their scan
     HIP_TRY(hipMemsetAsync(d_total_bits, 0, 4, ix->stream));
-    hipLaunchKernelGGL(bitmap_count_kernel, dim3(n_blocks), dim3(256), 0, ix->stream, g->visited, n_words, ix->dev.ids, ix->dev.n,
+    hipLaunchKernelGGL(bitmap_count_kernel, dim3(n_blocks), dim3(256), 0, ix->stream, bitmap, n_words, ix->dev.ids, ix->dev.n,
                        ix->contiguous ? 1u : 0u, ix->dev.dead, ix->pf_blocks, d_total_bits, d_block_bits);
     hipLaunchKernelGGL(block_scan_kernel, dim3(1), dim3(1024), 0, ix->stream, ix->pf_blocks, n_blocks);
     HIP_TRY(hipGetLastError());
@@ -1282,7 +1456,7 @@ static int prefilter_search_impl(const hvx_index *cix, const hvx_csr *cg, const 
         ix->cap_subset = n_rows;
     }
     if (n_rows)
-        hipLaunchKernelGGL(bitmap_compact_kernel, dim3(n_blocks), dim3(256), 0, ix->stream, g->visited, n_words, ix->dev.ids, ix->dev.n,
+        hipLaunchKernelGGL(bitmap_compact_kernel, dim3(n_blocks), dim3(256), 0, ix->stream, bitmap, n_words, ix->dev.ids, ix->dev.n,
                            ix->contiguous ? 1u : 0u, ix->dev.dead, ix->pf_blocks, ix->f_subset);
     HIP_TRY(hipGetLastError());
     // restricted_execution_plan_with_beam_percent (restricted.rs:426-453) over the candidate population
@@ -1302,11 +1476,241 @@ static int prefilter_search_impl(const hvx_index *cix, const hvx_csr *cg, const 
         }
         HIP_TRY(hipMemcpyAsync(ix->w_samples + ns, ranks.data(), (size_t)ns * 4, hipMemcpyHostToDevice, ix->stream));
         hipLaunchKernelGGL(block_scan_kernel, dim3(1), dim3(1024), 0, ix->stream, d_block_bits, n_blocks);
-        hipLaunchKernelGGL(bitmap_select_kernel, dim3((ns + 63u) / 64u), dim3(64), 0, ix->stream, g->visited, n_words, d_block_bits, n_blocks,
+        hipLaunchKernelGGL(bitmap_select_kernel, dim3((ns + 63u) / 64u), dim3(64), 0, ix->stream, bitmap, n_words, d_block_bits, n_blocks,
                            ix->dev.ids, ix->dev.n, ix->contiguous ? 1u : 0u, ix->dev.dead, ix->w_samples + ns, ns, ix->w_samples);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(ix->stream)); // `ranks` lives on this frame
         d_samples = ix->w_samples;
     }
     return restricted_run_plan(ix, queries, b, k, plan, ix->f_subset, n_rows, d_samples, out_ids, out_scores, out_counts, out_status, rstats, stats);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Chains of expand hops: Access -> Expand -> ... -> Expand -> optional Filter -> VectorSearch (expand.rs:16-80, node output).
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+constexpr uint32_t kMaxPathHops = 16;
+
+struct PathPlan {
+    uint32_t n_hops = 0, n_labels = 0;
+    const uint32_t *direction = nullptr, *label_off = nullptr, *labels = nullptr;
+    uint32_t lab0(uint32_t i) const { return label_off ? label_off[i] : 0u; }
+    uint32_t lab_n(uint32_t i) const { return label_off ? label_off[i + 1] - label_off[i] : 0u; }
+};
+
+// the argument rules of both entry points: nothing is enqueued, nothing of the graph is touched
+int path_check(const hvx_csr *g, const uint64_t *seeds, uint32_t n_seeds, uint32_t n_hops, const uint32_t *hop_direction,
+               const uint32_t *hop_label_offsets, const uint32_t *hop_labels, PathPlan *p) {
+    if (n_hops == 0 || n_hops > kMaxPathHops) return fail(HVX_ERR_INVARIANT, "a chain has 1 .. %u hops, not %u", kMaxPathHops, n_hops);
+    if (!hop_direction) return fail(HVX_ERR_INVARIANT, "null argument");
+    if (std::max(g->max_out_deg, g->max_in_deg) >= (1ull << 31)) // (the hop kernel counts the arcs of one row in 32 bits)
+        return fail(HVX_ERR_UNSUPPORTED, "a chain of hops serves adjacency rows below 2^31 arcs");
+    for (uint32_t i = 0; i < n_hops; ++i)
+        if (hop_direction[i] > HVX_DIR_BOTH) return fail(HVX_ERR_INVARIANT, "bad direction on hop %u", i);
+    if (hop_label_offsets) {
+        for (uint32_t i = 0; i < n_hops; ++i)
+            if (hop_label_offsets[i + 1] < hop_label_offsets[i]) return fail(HVX_ERR_INVARIANT, "label offsets do not ascend at hop %u", i);
+        if (hop_label_offsets[n_hops] != 0 && !hop_labels) return fail(HVX_ERR_INVARIANT, "null labels");
+    }
+    if (n_seeds && !seeds) return fail(HVX_ERR_INVARIANT, "null seeds");
+    for (uint32_t i = 0; i < n_seeds; ++i)
+        if (seeds[i] >= g->n) return fail(HVX_ERR_INVARIANT, "unknown node %llu", (unsigned long long)seeds[i]);
+    p->n_hops = n_hops;
+    p->direction = hop_direction;
+    p->label_off = hop_label_offsets;
+    p->labels = hop_labels;
+    p->n_labels = hop_label_offsets ? hop_label_offsets[n_hops] : 0u;
+    return HVX_OK;
+}
+
+// min(n_nodes, n_seeds x the product of every hop's largest row), saturating: what the chain can reach at most
+uint64_t path_bound(const hvx_csr *g, uint32_t n_seeds, const PathPlan &p) {
+    uint64_t bound = n_seeds;
+    for (uint32_t i = 0; i < p.n_hops; ++i) {
+        const uint64_t per = (p.direction[i] != HVX_DIR_IN ? g->max_out_deg : 0) + (p.direction[i] != HVX_DIR_OUT ? g->max_in_deg : 0);
+        if (per == 0 || bound == 0) return 0;
+        bound = bound > g->n / per ? g->n : std::min<uint64_t>(bound * per, g->n); // (bound * per >= n whenever bound > n / per)
+    }
+    return bound;
+}
+
+// caller holds g->mu: the chain's buffers, the seeds in the pinned buffer, labels and mask uploads enqueued on `s`
+int path_stage(hvx_csr *g, hipStream_t s, const uint64_t *seeds, uint32_t n_seeds, const PathPlan &p, const uint64_t *node_mask_words) {
+    HIP_TRY(hipSetDevice(g->device));
+    int rc;
+    const size_t words32 = std::max<size_t>(((g->n + 63) / 64) * 2, 2);
+    if (!g->visited2) {
+        if ((rc = csr_alloc(g, (void **)&g->visited2, words32 * 4))) return rc;
+        if ((rc = csr_alloc(g, (void **)&g->hop_cnt, kMaxPathHops * 4))) return rc;
+    }
+    if (!g->h_hops && hipHostMalloc((void **)&g->h_hops, kMaxPathHops * 4, hipHostMallocDefault) != hipSuccess)
+        return fail(HVX_ERR_DEVICE, "hipHostMalloc hop sizes");
+    if (n_seeds > g->cap_h_seeds) {
+        HIP_TRY(hipStreamSynchronize(s)); // no kernel still reads the old buffer
+        HIP_TRY(hipStreamSynchronize(g->stream));
+        if (g->h_seeds) (void)hipHostFree(g->h_seeds);
+        g->h_seeds = nullptr;
+        g->cap_h_seeds = 0;
+        const size_t want = std::max<size_t>((size_t)n_seeds + n_seeds / 2, 4096);
+        if (hipHostMalloc((void **)&g->h_seeds, want * 4, hipHostMallocDefault) != hipSuccess) return fail(HVX_ERR_DEVICE, "hipHostMalloc(%zu) seeds", want * 4);
+        g->cap_h_seeds = want;
+    }
+    for (uint32_t i = 0; i < n_seeds; ++i) g->h_seeds[i] = (uint32_t)seeds[i]; // (path_check has seen every one below n)
+    if ((rc = upload_labels(g, p.labels, p.n_labels, s))) return rc;
+    if (node_mask_words) {
+        if (!g->mask_dev && (rc = csr_alloc(g, (void **)&g->mask_dev, words32 * 4))) return rc;
+        if (!g->h_mask && hipHostMalloc((void **)&g->h_mask, words32 * 4, hipHostMallocDefault) != hipSuccess)
+            return fail(HVX_ERR_DEVICE, "hipHostMalloc(%zu) mask", words32 * 4);
+        memcpy(g->h_mask, node_mask_words, (size_t)((g->n + 63) / 64) * 8);
+        HIP_TRY(hipMemcpyAsync(g->mask_dev, g->h_mask, (size_t)((g->n + 63) / 64) * 8, hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(hipMemsetAsync(g->hop_cnt, 0, kMaxPathHops * 4, s));
+    return HVX_OK;
+}
+
+// Enqueues hops [0, n_run) of the chain on `s`; the bitmap of F(n_hops) lands in g->visited whatever the hop count's parity.
+// `collect` != NULL: the last hop is the lean route's (rows and counters filled in by the caller).
+int path_enqueue(hvx_csr *g, hipStream_t s, uint32_t n_seeds, const PathPlan &p, const PathHopArgs *collect) {
+    const size_t words32 = std::max<size_t>(((g->n + 63) / 64) * 2, 2);
+    const uint32_t grid_cap = 512; // (a workgroup takes 1 024 seeds or node numbers per pass)
+    for (uint32_t i = 0; i < p.n_hops; ++i) {
+        const bool last = i + 1 == p.n_hops;
+        uint32_t *dst = ((p.n_hops - 1 - i) & 1u) ? g->visited2 : g->visited, *src = dst == g->visited ? g->visited2 : g->visited;
+        PathHopArgs a;
+        memset(&a, 0, sizeof(a));
+        if (last && collect) a = *collect;
+        a.g = CsrView{g->out_off, g->in_off, g->out_tgt, g->in_tgt, g->out_lab, g->in_lab, g->n};
+        a.front = i == 0 ? g->h_seeds : src;
+        a.n_front = i == 0 ? n_seeds : g->n;
+        a.direction = p.direction[i];
+        a.allowed = g->labels + p.lab0(i);
+        a.n_allowed = p.lab_n(i);
+        a.dst = dst;
+        a.hop_size = g->hop_cnt + i;
+        HIP_TRY(hipMemsetAsync(dst, 0, words32 * 4, s));
+        const uint32_t blocks = std::max<uint32_t>(1u, (uint32_t)std::min<uint64_t>(grid_cap, ((uint64_t)a.n_front + 1023) / 1024));
+        if (i == 0) {
+            if (last && collect) hipLaunchKernelGGL((path_hop_kernel<false, true>), dim3(blocks), dim3(1024), 0, s, a);
+            else hipLaunchKernelGGL((path_hop_kernel<false, false>), dim3(blocks), dim3(1024), 0, s, a);
+        } else {
+            if (last && collect) hipLaunchKernelGGL((path_hop_kernel<true, true>), dim3(blocks), dim3(1024), 0, s, a);
+            else hipLaunchKernelGGL((path_hop_kernel<true, false>), dim3(blocks), dim3(1024), 0, s, a);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(g->h_hops, g->hop_cnt, kMaxPathHops * 4, hipMemcpyDeviceToHost, s));
+    return HVX_OK;
+}
+
+void path_sizes_out(const hvx_csr *g, uint32_t n_hops, uint64_t *out_hop_sizes) {
+    if (out_hop_sizes)
+        for (uint32_t i = 0; i < n_hops; ++i) out_hop_sizes[i] = g->h_hops[i];
+}
+
+} // namespace
+
+extern "C" int hvx_expand_path_filter(const hvx_csr *cg, const uint64_t *seeds, uint32_t n_seeds, uint32_t n_hops, const uint32_t *hop_direction,
+                                      const uint32_t *hop_label_offsets, const uint32_t *hop_labels, uint64_t *out_bitmap_words,
+                                      uint64_t *out_hop_sizes) {
+    if (!cg || !out_bitmap_words) return fail(HVX_ERR_INVARIANT, "null argument");
+    hvx_csr *g = const_cast<hvx_csr *>(cg);
+    PathPlan p;
+    int rc = path_check(g, seeds, n_seeds, n_hops, hop_direction, hop_label_offsets, hop_labels, &p);
+    if (rc) return rc;
+    const size_t bytes = (size_t)((g->n + 63) / 64) * 8;
+    if (n_seeds == 0) { // an empty stream expands to nothing
+        memset(out_bitmap_words, 0, bytes);
+        if (out_hop_sizes) memset(out_hop_sizes, 0, (size_t)n_hops * 8);
+        return HVX_OK;
+    }
+    std::lock_guard<std::mutex> lock(g->mu);
+    if ((rc = path_stage(g, g->stream, seeds, n_seeds, p, nullptr))) return rc;
+    if ((rc = path_enqueue(g, g->stream, n_seeds, p, nullptr))) return rc;
+    if (bytes) HIP_TRY(hipMemcpyAsync(out_bitmap_words, g->visited, bytes, hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    path_sizes_out(g, n_hops, out_hop_sizes);
+    return HVX_OK;
+}
+
+extern "C" int hvx_prefilter_path_search_batch_params(const hvx_index *cix, const hvx_csr *cg, const float *queries, uint32_t b,
+                                                      const hvx_restricted_params *params, const uint64_t *seeds, uint32_t n_seeds, uint32_t n_hops,
+                                                      const uint32_t *hop_direction, const uint32_t *hop_label_offsets, const uint32_t *hop_labels,
+                                                      const uint64_t *node_mask_words, uint64_t *out_ids, float *out_scores, uint32_t *out_counts,
+                                                      uint32_t *out_status, uint64_t *out_candidates, uint64_t *out_hop_sizes,
+                                                      hvx_restricted_stats *rstats, hvx_stats *stats) {
+    if (!cix || !cg || !params) return fail(HVX_ERR_INVARIANT, "null argument");
+    if (params->strategy > HVX_RESTRICTED_REFERENCE_PLAN) return fail(HVX_ERR_INVARIANT, "unknown restricted strategy %u", params->strategy);
+    const hvx_restricted_params &rp = *params;
+    hvx_index *ix = const_cast<hvx_index *>(cix);
+    hvx_csr *g = const_cast<hvx_csr *>(cg);
+    const uint32_t k = rp.k;
+    if (k == 0) return fail(HVX_ERR_K_RANGE, "result count must be non-zero");
+    if (rp.ef < k) return fail(HVX_ERR_K_RANGE, "search beam width %u is below the result count %u", rp.ef, k);
+    if (ix->device != g->device) return fail(HVX_ERR_INVARIANT, "index and graph live on different devices");
+    PathPlan p;
+    int rc = path_check(g, seeds, n_seeds, n_hops, hop_direction, hop_label_offsets, hop_labels, &p);
+    if (rc) return rc;
+    if (out_candidates) *out_candidates = 0;
+    if (out_hop_sizes) memset(out_hop_sizes, 0, (size_t)n_hops * 8);
+    for (uint32_t q = 0; q < b; ++q) {
+        out_counts[q] = 0;
+        if (out_status) out_status[q] = HVX_OK;
+        if (rstats) memset(&rstats[q], 0, sizeof(hvx_restricted_stats));
+    }
+    if (b == 0 || n_seeds == 0) return HVX_OK; // an empty stream expands to nothing
+    std::lock_guard<std::mutex> glock(g->mu);
+    std::lock_guard<std::mutex> lock(ix->mu);
+    ix->sync_rewrites();
+    hipStream_t s = ix->stream;
+    // the route: prefilter_search_impl's rule, over the chain's bound
+    bool lean = false;
+    uint64_t bound = 0;
+    if (ix->opt[HVX_OPT_RESTRICTED_DIRECT] != 1u && !rp.explicit_budgets &&
+        (k <= 64u || ix->opt[HVX_OPT_RESTRICTED_DIRECT] == 2u || !restricted_older_serves(ix, k)) && restricted_direct_supported(ix, k) &&
+        ix->dev.n != 0u) {
+        bound = path_bound(g, n_seeds, p);
+        RestrictedPlan plan;
+        const bool exact_any = bound == 0 || (bound <= 1000000ull && restricted_make_plan(rp, bound, ix->dev.dim, &plan, ix) == HVX_OK &&
+                                             plan.strategy == HVX_RESTRICTED_EXACT && (rp.strategy != HVX_RESTRICTED_REFERENCE_PLAN || bound <= 256));
+        const uint64_t work = (uint64_t)b * std::min<uint64_t>(bound, ix->dev.n) * ix->dev.dim;
+        lean = exact_any && bound != 0 && b <= ix->max_batch && (work <= (1ull << 28) || ix->opt[HVX_OPT_RESTRICTED_DIRECT] == 2u);
+    }
+    if ((rc = path_stage(g, s, seeds, n_seeds, p, node_mask_words))) return rc;
+    if (lean) { // every hop, the row list and the scan behind one host wait
+        const uint32_t rows_cap = (uint32_t)std::min<uint64_t>(bound, ix->dev.n);
+        if (rows_cap > ix->cap_subset) {
+            if ((rc = ix->regrow((void **)&ix->f_subset, (size_t)std::max<uint32_t>(rows_cap, 1u) * 4))) return rc;
+            ix->cap_subset = rows_cap;
+        }
+        if (ix->cap_pf_blocks < 4) {
+            if ((rc = ix->regrow((void **)&ix->pf_blocks, 64))) return rc;
+            ix->cap_pf_blocks = 16;
+        }
+        HIP_TRY(hipMemsetAsync(ix->pf_blocks, 0, 8, s));
+        PathHopArgs c;
+        memset(&c, 0, sizeof(c));
+        c.mask = node_mask_words ? g->mask_dev : nullptr;
+        c.ids = ix->dev.ids;
+        c.n = ix->dev.n;
+        c.contiguous = ix->contiguous ? 1u : 0u;
+        c.dead = ix->dev.dead;
+        c.rows_out = ix->f_subset;
+        c.rows_cap = rows_cap;
+        c.counters = ix->pf_blocks;
+        if ((rc = path_enqueue(g, s, n_seeds, p, &c))) return rc;
+        rc = restricted_direct_shared_devcount(ix, queries, b, k, ix->f_subset, rows_cap, ix->pf_blocks, out_ids, out_scores, out_counts, out_status,
+                                               out_candidates, rstats, stats);
+    } else {
+        if ((rc = path_enqueue(g, s, n_seeds, p, nullptr))) return rc;
+        if (node_mask_words) {
+            const uint32_t n_words = ((g->n + 63u) / 64u) * 2u;
+            hipLaunchKernelGGL(bitmap_and_kernel, dim3((n_words + 255u) / 256u), dim3(256), 0, s, g->visited, g->mask_dev, n_words);
+            HIP_TRY(hipGetLastError());
+        }
+        rc = prefilter_bitmap_route(ix, g, g->visited, queries, b, rp, out_ids, out_scores, out_counts, out_status, out_candidates, rstats, stats);
+    }
+    if (rc != HVX_OK && rc != HVX_ERR_CANDIDATE_LIMIT && rc != HVX_ERR_K_RANGE) (void)hipStreamSynchronize(s); // (a refusal in front of the route's wait)
+    path_sizes_out(g, n_hops, out_hop_sizes);
+    return rc;
 }

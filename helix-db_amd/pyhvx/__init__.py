@@ -359,6 +359,11 @@ def lib():
     L.hvx_prefilter_search_batch_params.argtypes = [_vp, _vp, _vp, C.c_uint32, C.POINTER(RestrictedParams), C.c_uint32, _vp, C.c_uint32,
                                                     C.c_uint32, C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp,
                                                     C.POINTER(C.c_uint64), _vp, C.POINTER(Stats)]
+    L.hvx_prefilter_path_search_batch_params.restype = C.c_int
+    L.hvx_prefilter_path_search_batch_params.argtypes = [_vp, _vp, _vp, C.c_uint32, C.POINTER(RestrictedParams), _vp, C.c_uint32, C.c_uint32, _vp, _vp,
+                                                         _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_uint64), _vp, _vp, C.POINTER(Stats)]
+    L.hvx_expand_path_filter.restype = C.c_int
+    L.hvx_expand_path_filter.argtypes = [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp]
     L.hvx_batcher_new.restype = C.c_int
     L.hvx_batcher_new.argtypes = [_vp, C.POINTER(_Params), C.c_uint32, C.c_uint32, C.POINTER(_vp)]
     L.hvx_batcher_free.argtypes = [_vp]
@@ -902,6 +907,44 @@ class ValidatedVectorReadIndex:
                                                 C.byref(ncand), C.byref(stats)))
         return ids, sc, cnt, int(ncand.value), stats.as_dict()
 
+    def prefilter_path_search_batch_params(self, graph: "Graph", queries, rparams: "RestrictedParams", seeds, hops, node_mask=None,
+                                           want_stats=False, want_sizes=False):
+        """Access -> Expand -> ... -> Expand -> optional Filter -> vector_search in ONE call (hvx_prefilter_path_search_batch_params):
+        `hops` = [(direction, allowed_labels)] (a bare direction means every label), `node_mask` = bitmap words over the graph's nodes
+        (u64, as Graph.expand returns them) ANDed with the last hop's nodes.  Every frontier stays on the device.  Returns (ids, scores,
+        counts, n_candidates, [RestrictedSearchStats dicts]) (+ the hvx_stats dict when want_stats) (+ the per-hop frontier sizes,
+        unmasked, when want_sizes).  A refused call raises HelixDbError carrying `n_candidates` and `hop_sizes` as far as they were known."""
+        q = self._q(queries)
+        b, k = q.shape[0], int(rparams.k)
+        s = np.ascontiguousarray(seeds, dtype=np.uint64)
+        dirs, offs, labs = _path_hops(hops)
+        mask = None if node_mask is None else np.ascontiguousarray(node_mask, dtype=np.uint64)
+        if mask is not None and mask.size != (graph.n + 63) // 64:
+            raise HelixDbError(ERR_INVARIANT, f"the node mask holds {mask.size} words, the graph {(graph.n + 63) // 64}")
+        ids = np.zeros((b, k), np.uint64); sc = np.zeros((b, k), np.float32); cnt = np.zeros(b, np.uint32)
+        ncand = C.c_uint64(0)
+        sizes = np.zeros(max(dirs.size, 1), np.uint64)
+        rs = (RestrictedStats * b)()
+        stats = Stats()
+        rc = lib().hvx_prefilter_path_search_batch_params(self._h, graph._h, _ptr(q), b, C.byref(rparams), _ptr(s), s.size, dirs.size, _ptr(dirs),
+                                                          _ptr(offs), _ptr(labs), _ptr(mask), _ptr(ids), _ptr(sc), _ptr(cnt), None,
+                                                          C.byref(ncand), _ptr(sizes), C.cast(rs, _vp), C.byref(stats))
+        if rc != OK:
+            err = HelixDbError(rc, lib().hvx_last_error().decode())
+            err.n_candidates, err.hop_sizes = int(ncand.value), sizes[: dirs.size].tolist()
+            raise err
+        out = (ids, sc, cnt, int(ncand.value), [r.as_dict() for r in rs])
+        if want_stats:
+            out += (stats.as_dict(),)
+        return out + (sizes[: dirs.size].tolist(),) if want_sizes else out
+
+    def prefilter_path_search_batch(self, graph: "Graph", queries, params: SearchParams, seeds, hops, node_mask=None, want_sizes=False):
+        """the chain of hops + the exact scan whatever the candidate count (what prefilter_search_batch is to one hop); returns
+        (ids, scores, counts, n_candidates, stats) (+ the per-hop frontier sizes when want_sizes)"""
+        rp = RestrictedParams(k=params.k, ef=params.ef, strategy=RESTRICTED_EXACT)
+        out = self.prefilter_path_search_batch_params(graph, queries, rp, seeds, hops, node_mask, want_stats=True, want_sizes=want_sizes)
+        return out[:4] + out[5:]
+
     # ---- device-resident surface (torch tensors on the index's GPU) ----
     def search_batch_device(self, d_queries, k, ef, d_ids, d_scores, d_counts, d_status, d_qstats=None, want_stats=False):
         stats = Stats()
@@ -1309,6 +1352,27 @@ class Graph:
         words = np.zeros((self.n + 63) // 64, np.uint64)
         _check(lib().hvx_expand_filter(self._h, _ptr(s), s.size, direction, _ptr(lab), lab.size, _ptr(words)))
         return words
+
+    def expand_path(self, seeds, hops, want_sizes=False):
+        """A chain of `expand` hops on the device (hvx_expand_path_filter): `hops` = [(direction, allowed_labels)].  Returns the bitmap
+        words of the LAST hop's nodes (+ every hop's frontier size when want_sizes); no visited exclusion between the hops."""
+        s = np.ascontiguousarray(seeds, dtype=np.uint64)
+        dirs, offs, labs = _path_hops(hops)
+        words = np.zeros((self.n + 63) // 64, np.uint64)
+        sizes = np.zeros(max(dirs.size, 1), np.uint64)
+        _check(lib().hvx_expand_path_filter(self._h, _ptr(s), s.size, dirs.size, _ptr(dirs), _ptr(offs), _ptr(labs), _ptr(words), _ptr(sizes)))
+        return (words, sizes[: dirs.size].tolist()) if want_sizes else words
+
+
+def _path_hops(hops):
+    """[(direction, allowed_labels)] -> the parallel arrays of the C ABI: directions, label offsets, labels"""
+    dirs, offs, labs = [], [0], []
+    for h in hops:
+        d, allowed = (h, ()) if isinstance(h, (int, np.integer)) else h
+        dirs.append(int(d))
+        labs.extend(int(x) for x in (allowed or ()))
+        offs.append(len(labs))
+    return np.asarray(dirs, np.uint32), np.asarray(offs, np.uint32), np.asarray(labs if labs else [0], np.uint32)
 
 
 class SimHasher:

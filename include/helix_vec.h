@@ -526,6 +526,34 @@ int hvx_prefilter_search_batch_params(const hvx_index *, const hvx_csr *, const 
                                       uint32_t *out_counts, uint32_t *out_status /*nullable*/, uint64_t *out_candidates /*nullable*/,
                                       hvx_restricted_stats *out_restricted_stats /*[b] nullable*/, hvx_stats *stats);
 
+/* A chain of `expand` hops (expand.rs:16-80, node output), set semantics:
+ *   F0 = the distinct seeds;  F(i+1) = union over v in F(i) of the neighbours of v in hop_direction[i] whose edge label is in hop i's allow-set
+ * Hop i's allow-set is hop_labels[hop_label_offsets[i] .. hop_label_offsets[i+1]).  An empty range means every label.
+ * hop_label_offsets == NULL means every label on every hop.
+ * No visited exclusion: a node of F(i) is in F(i+1) iff an arc reaches it, and it may be in both.
+ * A node without arcs drops out.  Intermediate nodes need not hold vectors.
+ * Writes the bitmap of F(n_hops) in hvx_expand_filter's format.
+ * When out_hop_sizes != NULL, also writes |F(1)| .. |F(n_hops)|.
+ * n_hops is 1 .. 16; a bad hop count, direction or descending label offsets, or an unknown seed: HVX_ERR_INVARIANT before anything runs.
+ * n_seeds == 0: HVX_OK, an empty bitmap and zero sizes. */
+int hvx_expand_path_filter(const hvx_csr *, const uint64_t *seeds, uint32_t n_seeds, uint32_t n_hops,
+                           const uint32_t *hop_direction /*[n_hops]*/, const uint32_t *hop_label_offsets /*[n_hops+1] or NULL*/,
+                           const uint32_t *hop_labels, uint64_t *out_bitmap_words, uint64_t *out_hop_sizes /*[n_hops] nullable*/);
+
+/* The chain, then the optional Filter step, then restricted kNN, in one call.
+ * node_mask: bitmap words in the same format, one bit per CSR node.  NULL means keep all.
+ * Candidates = F(n_hops) AND node_mask.  Every intermediate frontier stays on the device: no frontier size comes back to the host
+ * between two hops.  out_hop_sizes (unmasked) is filled on every route.
+ * params, statuses, limits (<= 1 000 000 candidates, k <= 800 after clamping to the population), out_candidates and
+ * out_restricted_stats are exactly as for hvx_prefilter_search_batch_params in HVX_PREFILTER_EXPAND mode. */
+int hvx_prefilter_path_search_batch_params(const hvx_index *, const hvx_csr *, const float *queries, uint32_t b,
+                                           const hvx_restricted_params *params, const uint64_t *seeds, uint32_t n_seeds,
+                                           uint32_t n_hops, const uint32_t *hop_direction, const uint32_t *hop_label_offsets,
+                                           const uint32_t *hop_labels, const uint64_t *node_mask_words /*nullable*/,
+                                           uint64_t *out_ids, float *out_scores, uint32_t *out_counts, uint32_t *out_status /*nullable*/,
+                                           uint64_t *out_candidates /*nullable*/, uint64_t *out_hop_sizes /*[n_hops] nullable*/,
+                                           hvx_restricted_stats *out_restricted_stats /*[b] nullable*/, hvx_stats *stats);
+
 /*
  * Batching operator: the reference calls ValidatedVectorReadIndex::search once per operator invocation
  * from many tokio tasks (access/search/storage.rs:140-163).  Concurrent single-query callers are coalesced into ONE
