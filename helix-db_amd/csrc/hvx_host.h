@@ -313,6 +313,28 @@ int restricted_direct_enqueue(hvx_index *ix, const float *d_queries, uint32_t b,
 int restricted_direct_shared_devcount(hvx_index *ix, const float *queries, uint32_t b, uint32_t k, const uint32_t *d_rows, uint32_t rows_cap,
                                       const uint32_t *d_counters, uint64_t *out_ids, float *out_scores, uint32_t *out_counts, uint32_t *out_status,
                                       uint64_t *out_candidates, hvx_restricted_stats *rstats, hvx_stats *stats);
+// ... over per-query id lists that live on the device in fixed slots (d_ids[q * stride ..), d_ctl[q] <= stride ids each: the batched chain
+// kernel's output): host-resident queries, results and the `ctl_words` words at d_ctl (the b list lengths first; copied into ix->h_flags)
+// delivered with ONE stream wait.  Fills out_counts / out_status (the scan's own: 0 for an empty list) and the result rows; the caller
+// reads ix->h_flags.
+int restricted_direct_lists_devlens(hvx_index *ix, const float *queries, uint32_t b, uint32_t k, const uint64_t *d_ids, uint32_t stride,
+                                    const uint32_t *d_ctl, size_t ctl_words, uint64_t *out_ids, float *out_scores, uint32_t *out_counts,
+                                    uint32_t *out_status, hvx_stats *stats);
+// The batched chain kernel (hvx_prefilter_batch.hip): one workgroup per query walks the query's own chain of hops.
+struct PathListsArgs {
+    const uint64_t *out_off, *in_off;                 // the CSR, both adjacencies
+    const uint32_t *out_tgt, *in_tgt, *out_lab, *in_lab;
+    const uint32_t *seeds, *seed_off;                 // pinned host memory: every query's seeds back to back, [b + 1] offsets into them
+    uint32_t n_hops, direction[16], label_off[17];    // the plan the batch shares; hop i's allow-set = labels[label_off[i] .. label_off[i + 1])
+    const uint32_t *labels;
+    const uint32_t *mask;                             // nullable: the Filter step's node mask (bitmap words)
+    uint32_t max_frontier;                            // ids per slot, at most 16 384
+    uint32_t slots, hash_shift;                       // (filled in by launch_path_lists)
+    uint32_t *front;                                  // [b][2][max_frontier] the frontier lists
+    unsigned long long *out_ids;                      // [b][max_frontier] the final set AND mask, as the scan's external ids
+    uint32_t *lens, *status, *hop_sizes;              // [b] ids in the slot, [b] HVX_OK / HVX_ERR_CANDIDATE_LIMIT, [b][16] |F(i + 1)|
+};
+hipError_t launch_path_lists(const PathListsArgs &args, uint32_t b, hipStream_t s);
 hipError_t launch_stage_ids(const uint64_t *src, const uint32_t *lens, uint32_t stride, uint64_t *dst, uint32_t b, hipStream_t s);
 // exact tail of the small-batch matrix-core scan (hvx_flat_tail.hip): k <= 64, AVX+FMA tree, L2 / cosine, f32 or bf16 rows
 bool flat_tail_supported(const hvx_index *ix, uint32_t b, uint32_t k, uint32_t n_rows);

@@ -58,6 +58,10 @@ struct hvx_csr {
     uint32_t *mask_dev = nullptr;                   // [words] the Filter step's node mask
     uint32_t *h_mask = nullptr;                     // pinned staging of the mask
     uint32_t *h_hops = nullptr;                     // pinned [16]: the hop sizes read back
+    // chains with per-query seeds (hvx_expand_path_lists / hvx_prefilter_path_search_lists_params), allocated on first use, grown on demand:
+    // [b][max_frontier] u64 scan slots | [b][2][max_frontier] u32 frontier lists | [b] lengths | [b] statuses | [b][16] hop sizes
+    void *lists_buf = nullptr;
+    size_t lists_cap = 0;
 };
 
 namespace {
@@ -1713,4 +1717,181 @@ extern "C" int hvx_prefilter_path_search_batch_params(const hvx_index *cix, cons
     if (rc != HVX_OK && rc != HVX_ERR_CANDIDATE_LIMIT && rc != HVX_ERR_K_RANGE) (void)hipStreamSynchronize(s); // (a refusal in front of the route's wait)
     path_sizes_out(g, n_hops, out_hop_sizes);
     return rc;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Chains with per-query seeds: the same plan (hops, labels, Filter step) for every request of a batch, each request from its own start
+// nodes -- the batching operator's prefiltered branch (storage.rs:140-163) with the traversal in front of it.  One launch of
+// path_lists_kernel (hvx_prefilter_batch.hip) runs every chain and leaves query q's final set in slot q of the one-launch scan.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+constexpr uint32_t kMaxListFrontier = 16384; // 32 768 table slots x 4 B = 128 KiB of a CU's 160 KiB of LDS
+constexpr uint32_t kMaxListBatch = 65535;    // (seed offsets and slot positions stay inside 32 bits)
+
+// the argument rules of both entry points: nothing is enqueued, nothing of the graph is touched
+int lists_check(const hvx_csr *g, uint32_t b, const uint64_t *seeds, const uint64_t *seed_offsets, uint32_t n_hops, const uint32_t *hop_direction,
+                const uint32_t *hop_label_offsets, const uint32_t *hop_labels, uint32_t max_frontier, PathPlan *p) {
+    int rc = path_check(g, nullptr, 0, n_hops, hop_direction, hop_label_offsets, hop_labels, p);
+    if (rc) return rc;
+    if (!seed_offsets) return fail(HVX_ERR_INVARIANT, "null argument");
+    if (max_frontier == 0 || max_frontier > kMaxListFrontier)
+        return fail(HVX_ERR_UNSUPPORTED, "per-query chains keep sets of 1 .. %u nodes (max_frontier %u): larger sets take the shared-seed call", kMaxListFrontier, max_frontier);
+    if (b > kMaxListBatch) return fail(HVX_ERR_UNSUPPORTED, "a batch of per-query chains holds at most %u queries", kMaxListBatch);
+    for (uint32_t q = 0; q < b; ++q) {
+        if (seed_offsets[q + 1] < seed_offsets[q]) return fail(HVX_ERR_INVARIANT, "seed offsets do not ascend at query %u", q);
+        if (seed_offsets[q + 1] - seed_offsets[q] > max_frontier)
+            return fail(HVX_ERR_INVARIANT, "query %u starts from %llu seeds, its slot holds %u", q, (unsigned long long)(seed_offsets[q + 1] - seed_offsets[q]), max_frontier);
+    }
+    if (b && seed_offsets[b] != seed_offsets[0] && !seeds) return fail(HVX_ERR_INVARIANT, "null seeds");
+    for (uint64_t i = b ? seed_offsets[0] : 0; b && i < seed_offsets[b]; ++i)
+        if (seeds[i] >= g->n) return fail(HVX_ERR_INVARIANT, "unknown node %llu", (unsigned long long)seeds[i]);
+    return HVX_OK;
+}
+
+struct ListsView { uint64_t *ids; uint32_t *front, *ctl; size_t ctl_words; }; // ctl = [b] lengths | [b] statuses | [b][16] hop sizes
+
+// caller holds g->mu; b != 0.  Seeds and offsets into the pinned buffer, labels and mask uploads and the chain kernel enqueued on `s`.
+int lists_enqueue(hvx_csr *g, hipStream_t s, uint32_t b, const uint64_t *seeds, const uint64_t *seed_offsets, const PathPlan &p,
+                  const uint64_t *node_mask_words, uint32_t max_frontier, ListsView *view) {
+    HIP_TRY(hipSetDevice(g->device));
+    int rc;
+    const uint64_t first = seed_offsets[0], total = seed_offsets[b] - first;
+    const size_t want = (size_t)b + 1 + total;
+    if (want > g->cap_h_seeds) {
+        HIP_TRY(hipStreamSynchronize(s)); // no kernel still reads the old buffer
+        HIP_TRY(hipStreamSynchronize(g->stream));
+        if (g->h_seeds) (void)hipHostFree(g->h_seeds);
+        g->h_seeds = nullptr;
+        g->cap_h_seeds = 0;
+        const size_t cap = std::max<size_t>(want + want / 2, 4096);
+        if (hipHostMalloc((void **)&g->h_seeds, cap * 4, hipHostMallocDefault) != hipSuccess) return fail(HVX_ERR_DEVICE, "hipHostMalloc(%zu) seeds", cap * 4);
+        g->cap_h_seeds = cap;
+    }
+    uint32_t *h_off = g->h_seeds, *h_seed = g->h_seeds + b + 1;
+    for (uint32_t q = 0; q <= b; ++q) h_off[q] = (uint32_t)(seed_offsets[q] - first);
+    for (uint64_t i = 0; i < total; ++i) h_seed[i] = (uint32_t)seeds[first + i]; // (lists_check has seen every one below n)
+    if ((rc = upload_labels(g, p.labels, p.n_labels, s))) return rc;
+    if (node_mask_words) {
+        const size_t words32 = std::max<size_t>(((g->n + 63) / 64) * 2, 2);
+        if (!g->mask_dev && (rc = csr_alloc(g, (void **)&g->mask_dev, words32 * 4))) return rc;
+        if (!g->h_mask && hipHostMalloc((void **)&g->h_mask, words32 * 4, hipHostMallocDefault) != hipSuccess)
+            return fail(HVX_ERR_DEVICE, "hipHostMalloc(%zu) mask", words32 * 4);
+        memcpy(g->h_mask, node_mask_words, (size_t)((g->n + 63) / 64) * 8);
+        HIP_TRY(hipMemcpyAsync(g->mask_dev, g->h_mask, (size_t)((g->n + 63) / 64) * 8, hipMemcpyHostToDevice, s));
+    }
+    const size_t slots = (size_t)b * max_frontier;
+    view->ctl_words = (size_t)b * (2 + kMaxPathHops);
+    const size_t bytes = slots * 8 + slots * 2 * 4 + view->ctl_words * 4;
+    if (bytes > g->lists_cap) {
+        if (g->lists_buf) { // (every call that used it has waited for its stream)
+            g->allocs.erase(std::remove(g->allocs.begin(), g->allocs.end(), g->lists_buf), g->allocs.end());
+            (void)hipFree(g->lists_buf);
+            g->lists_buf = nullptr;
+            g->lists_cap = 0;
+        }
+        if ((rc = csr_alloc(g, &g->lists_buf, bytes))) return rc;
+        g->lists_cap = bytes;
+    }
+    view->ids = static_cast<uint64_t *>(g->lists_buf);
+    view->front = reinterpret_cast<uint32_t *>(view->ids + slots);
+    view->ctl = view->front + slots * 2;
+    PathListsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.out_off = g->out_off; a.in_off = g->in_off;
+    a.out_tgt = g->out_tgt; a.in_tgt = g->in_tgt; a.out_lab = g->out_lab; a.in_lab = g->in_lab;
+    a.seeds = h_seed; a.seed_off = h_off;
+    a.n_hops = p.n_hops;
+    for (uint32_t i = 0; i < p.n_hops; ++i) { a.direction[i] = p.direction[i]; a.label_off[i] = p.lab0(i); a.label_off[i + 1] = p.lab0(i) + p.lab_n(i); }
+    a.labels = g->labels;
+    a.mask = node_mask_words ? g->mask_dev : nullptr;
+    a.max_frontier = max_frontier;
+    a.front = view->front;
+    a.out_ids = reinterpret_cast<unsigned long long *>(view->ids);
+    a.lens = view->ctl; a.status = view->ctl + b; a.hop_sizes = view->ctl + 2 * (size_t)b;
+    HIP_TRY(launch_path_lists(a, b, s));
+    return HVX_OK;
+}
+
+void lists_sizes_out(const uint32_t *ctl, uint32_t b, uint32_t n_hops, uint64_t *out_hop_sizes) {
+    if (!out_hop_sizes) return;
+    for (uint32_t q = 0; q < b; ++q)
+        for (uint32_t i = 0; i < n_hops; ++i) out_hop_sizes[(size_t)q * n_hops + i] = ctl[2 * (size_t)b + (size_t)q * kMaxPathHops + i];
+}
+
+} // namespace
+
+extern "C" int hvx_expand_path_lists(const hvx_csr *cg, uint32_t b, const uint64_t *seeds, const uint64_t *seed_offsets, uint32_t n_hops,
+                                     const uint32_t *hop_direction, const uint32_t *hop_label_offsets, const uint32_t *hop_labels,
+                                     const uint64_t *node_mask_words, uint32_t max_frontier, uint64_t *out_ids, uint32_t *out_lens,
+                                     uint32_t *out_status, uint64_t *out_hop_sizes) {
+    if (!cg || !out_ids || !out_lens || !out_status) return fail(HVX_ERR_INVARIANT, "null argument");
+    hvx_csr *g = const_cast<hvx_csr *>(cg);
+    PathPlan p;
+    int rc = lists_check(g, b, seeds, seed_offsets, n_hops, hop_direction, hop_label_offsets, hop_labels, max_frontier, &p);
+    if (rc) return rc;
+    if (b == 0) return HVX_OK;
+    std::lock_guard<std::mutex> lock(g->mu);
+    ListsView v;
+    if ((rc = lists_enqueue(g, g->stream, b, seeds, seed_offsets, p, node_mask_words, max_frontier, &v))) {
+        (void)hipStreamSynchronize(g->stream);
+        return rc;
+    }
+    std::vector<uint32_t> ctl(v.ctl_words);
+    HIP_TRY(hipMemcpyAsync(ctl.data(), v.ctl, v.ctl_words * 4, hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipMemcpyAsync(out_ids, v.ids, (size_t)b * max_frontier * 8, hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    for (uint32_t q = 0; q < b; ++q) { out_lens[q] = ctl[q]; out_status[q] = ctl[b + q]; }
+    lists_sizes_out(ctl.data(), b, n_hops, out_hop_sizes);
+    return HVX_OK;
+}
+
+extern "C" int hvx_prefilter_path_search_lists_params(const hvx_index *cix, const hvx_csr *cg, const float *queries, uint32_t b,
+                                                      const hvx_restricted_params *params, const uint64_t *seeds, const uint64_t *seed_offsets,
+                                                      uint32_t n_hops, const uint32_t *hop_direction, const uint32_t *hop_label_offsets,
+                                                      const uint32_t *hop_labels, const uint64_t *node_mask_words, uint32_t max_frontier,
+                                                      uint64_t *out_ids, float *out_scores, uint32_t *out_counts, uint32_t *out_status,
+                                                      uint64_t *out_candidates, uint64_t *out_hop_sizes, hvx_stats *stats) {
+    if (!cix || !cg || !params || !out_ids || !out_scores || !out_counts || !out_status || (b && !queries)) return fail(HVX_ERR_INVARIANT, "null argument");
+    if (params->strategy > HVX_RESTRICTED_REFERENCE_PLAN) return fail(HVX_ERR_INVARIANT, "unknown restricted strategy %u", params->strategy);
+    hvx_index *ix = const_cast<hvx_index *>(cix);
+    hvx_csr *g = const_cast<hvx_csr *>(cg);
+    const uint32_t k = params->k;
+    if (k == 0) return fail(HVX_ERR_K_RANGE, "result count must be non-zero");
+    if (params->ef < k) return fail(HVX_ERR_K_RANGE, "search beam width %u is below the result count %u", params->ef, k);
+    if (ix->device != g->device) return fail(HVX_ERR_INVARIANT, "index and graph live on different devices");
+    PathPlan p;
+    int rc = lists_check(g, b, seeds, seed_offsets, n_hops, hop_direction, hop_label_offsets, hop_labels, max_frontier, &p);
+    if (rc) return rc;
+    if (b > ix->max_batch) return fail(HVX_ERR_UNSUPPORTED, "batch %u exceeds max_batch %u given at import", b, ix->max_batch);
+    std::lock_guard<std::mutex> glock(g->mu);
+    std::lock_guard<std::mutex> lock(ix->mu);
+    ix->sync_rewrites();
+    // this call IS the exact scan (as hvx_batcher_new_restricted): a plan that would walk a set of max_frontier ids is not served
+    RestrictedPlan plan;
+    if (params->strategy == HVX_RESTRICTED_FILTERED || params->strategy == HVX_RESTRICTED_REFERENCE_PLAN || params->explicit_budgets ||
+        restricted_make_plan(*params, max_frontier, ix->dev.dim, &plan, ix) != HVX_OK || plan.strategy != HVX_RESTRICTED_EXACT)
+        return fail(HVX_ERR_UNSUPPORTED, "per-query chains are answered by the exact scan: strategy EXACT, or AUTO with max_frontier x row bytes within the "
+                    "device plan's limit, and no explicit budgets");
+    if (!restricted_direct_supported(ix, k))
+        return fail(HVX_ERR_UNSUPPORTED, "the one-launch restricted scan serves k <= 800 over f32 / bf16 rows of a non-empty image");
+    if (b == 0) return HVX_OK;
+    hipStream_t s = ix->stream;
+    ListsView v;
+    if ((rc = lists_enqueue(g, s, b, seeds, seed_offsets, p, node_mask_words, max_frontier, &v)) ||
+        (rc = restricted_direct_lists_devlens(ix, queries, b, k, v.ids, max_frontier, v.ctl, v.ctl_words, out_ids, out_scores, out_counts,
+                                              out_status, stats))) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    const uint32_t *ctl = ix->h_flags;
+    for (uint32_t q = 0; q < b; ++q) {
+        if (out_candidates) out_candidates[q] = ctl[q];
+        if (ctl[b + q] != HVX_OK) { // the chain outgrew its slot: this wins over what the scan made of the query vector
+            out_status[q] = ctl[b + q];
+            out_counts[q] = 0;
+        }
+    }
+    lists_sizes_out(ctl, b, n_hops, out_hop_sizes);
+    return HVX_OK;
 }

@@ -870,6 +870,40 @@ int hvx::restricted_direct_shared_devcount(hvx_index *ix, const float *queries, 
     return HVX_OK;
 }
 
+int hvx::restricted_direct_lists_devlens(hvx_index *ix, const float *queries, uint32_t b, uint32_t k, const uint64_t *d_ids, uint32_t stride,
+                                         const uint32_t *d_ctl, size_t ctl_words, uint64_t *out_ids, float *out_scores, uint32_t *out_counts,
+                                         uint32_t *out_status, hvx_stats *stats) {
+    int rc;
+    if ((rc = ix->stage(b, k))) return rc;
+    PinView v;
+    if ((rc = pin_view(ix, b, k, &v))) return rc;
+    if ((rc = ix->pin_flags(ctl_words))) return rc;
+    if ((rc = stage_and_validate(ix, queries, b, v))) return rc;
+    if (stats) HIP_TRY(hipEventRecord(ix->ev0, ix->stream));
+    // (the grid is sized for the slot: the host never learns a list's length before the scan runs)
+    if ((rc = restricted_direct_enqueue(ix, ix->s_queries, b, k, k, nullptr, 0, d_ids, nullptr, stride, v.ids, v.sc, v.cnt, v.st, d_ctl, stride))) return rc;
+    if (stats) HIP_TRY(hipEventRecord(ix->ev1, ix->stream));
+    HIP_TRY(hipMemcpyAsync(ix->h_flags, d_ctl, ctl_words * 4, hipMemcpyDeviceToHost, ix->stream));
+    HIP_TRY(hipStreamSynchronize(ix->stream));
+    for (uint32_t q = 0; q < b; ++q) {
+        out_status[q] = v.st[q];
+        out_counts[q] = v.st[q] ? 0u : v.cnt[q];
+        memcpy(out_ids + (size_t)q * k, v.ids + (size_t)q * k, (size_t)out_counts[q] * 8);
+        memcpy(out_scores + (size_t)q * k, v.sc + (size_t)q * k, (size_t)out_counts[q] * 4);
+    }
+    if (stats) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, ix->ev0, ix->ev1));
+        uint64_t rows = 0;
+        for (uint32_t q = 0; q < b; ++q) rows += ix->h_flags[q];
+        stats->queries += b;
+        stats->vectors_loaded += rows;
+        stats->distance_computations += rows;
+        stats->device_ms += ms;
+    }
+    return HVX_OK;
+}
+
 int hvx::restricted_make_plan(const hvx_restricted_params &rp, uint64_t candidates, uint32_t dim, RestrictedPlan *out, const hvx_index *ix) {
     return make_plan(rp, candidates, dim, out, ix);
 }

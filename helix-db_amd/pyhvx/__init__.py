@@ -364,6 +364,11 @@ def lib():
                                                          _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_uint64), _vp, _vp, C.POINTER(Stats)]
     L.hvx_expand_path_filter.restype = C.c_int
     L.hvx_expand_path_filter.argtypes = [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp]
+    L.hvx_expand_path_lists.restype = C.c_int
+    L.hvx_expand_path_lists.argtypes = [_vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp]
+    L.hvx_prefilter_path_search_lists_params.restype = C.c_int
+    L.hvx_prefilter_path_search_lists_params.argtypes = [_vp, _vp, _vp, C.c_uint32, C.POINTER(RestrictedParams), _vp, _vp, C.c_uint32, _vp, _vp, _vp,
+                                                         _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(Stats)]
     L.hvx_batcher_new.restype = C.c_int
     L.hvx_batcher_new.argtypes = [_vp, C.POINTER(_Params), C.c_uint32, C.c_uint32, C.POINTER(_vp)]
     L.hvx_batcher_free.argtypes = [_vp]
@@ -945,6 +950,33 @@ class ValidatedVectorReadIndex:
         out = self.prefilter_path_search_batch_params(graph, queries, rp, seeds, hops, node_mask, want_stats=True, want_sizes=want_sizes)
         return out[:4] + out[5:]
 
+    def prefilter_path_search_lists(self, graph: "Graph", queries, params, seeds_per_query, hops, node_mask=None, max_frontier=4096,
+                                    want_sizes=False):
+        """The chain of hops for a batch of requests that share the plan and bring their OWN start nodes, then the exact scan of every
+        query over its own set, in one call (hvx_prefilter_path_search_lists_params).  `params`: SearchParams (the exact scan) or
+        RestrictedParams; `seeds_per_query`: one id sequence per query; `max_frontier` (<= 16 384) bounds every set of a chain.  Returns
+        (ids, scores, counts, statuses, n_candidates per query, stats) (+ [b][n_hops] frontier sizes, unmasked, when want_sizes).
+        A query whose chain outgrew max_frontier has status ERR_CANDIDATE_LIMIT and count 0; the call itself raises only when refused."""
+        q = self._q(queries)
+        rp = params if isinstance(params, RestrictedParams) else RestrictedParams(k=params.k, ef=params.ef, strategy=RESTRICTED_EXACT)
+        b, k = q.shape[0], int(rp.k)
+        s, soff = _seed_lists(seeds_per_query)
+        if soff.size != b + 1:
+            raise HelixDbError(ERR_INVARIANT, f"{soff.size - 1} seed lists for {b} queries")
+        dirs, offs, labs = _path_hops(hops)
+        mask = None if node_mask is None else np.ascontiguousarray(node_mask, dtype=np.uint64)
+        if mask is not None and mask.size != (graph.n + 63) // 64:
+            raise HelixDbError(ERR_INVARIANT, f"the node mask holds {mask.size} words, the graph {(graph.n + 63) // 64}")
+        ids = np.zeros((b, k), np.uint64); sc = np.zeros((b, k), np.float32); cnt = np.zeros(b, np.uint32); st = np.zeros(b, np.uint32)
+        ncand = np.zeros(b, np.uint64)
+        sizes = np.zeros((b, max(dirs.size, 1)), np.uint64)
+        stats = Stats()
+        _check(lib().hvx_prefilter_path_search_lists_params(self._h, graph._h, _ptr(q), b, C.byref(rp), _ptr(s), _ptr(soff), dirs.size, _ptr(dirs),
+                                                            _ptr(offs), _ptr(labs), _ptr(mask), int(max_frontier), _ptr(ids), _ptr(sc), _ptr(cnt),
+                                                            _ptr(st), _ptr(ncand), _ptr(sizes), C.byref(stats)))
+        out = (ids, sc, cnt, st, ncand, stats.as_dict())
+        return out + (sizes[:, : dirs.size],) if want_sizes else out
+
     # ---- device-resident surface (torch tensors on the index's GPU) ----
     def search_batch_device(self, d_queries, k, ef, d_ids, d_scores, d_counts, d_status, d_qstats=None, want_stats=False):
         stats = Stats()
@@ -1362,6 +1394,35 @@ class Graph:
         sizes = np.zeros(max(dirs.size, 1), np.uint64)
         _check(lib().hvx_expand_path_filter(self._h, _ptr(s), s.size, dirs.size, _ptr(dirs), _ptr(offs), _ptr(labs), _ptr(words), _ptr(sizes)))
         return (words, sizes[: dirs.size].tolist()) if want_sizes else words
+
+
+    def expand_path_lists(self, seeds_per_query, hops, max_frontier, node_mask=None):
+        """Chains of `expand` hops for a batch of queries that share `hops` and start from their OWN seeds (hvx_expand_path_lists).
+        Returns ([ids of query q's last set AND node_mask, in no particular order], statuses, [b][n_hops] frontier sizes, unmasked).  A
+        query whose chain outgrew max_frontier (<= 16 384) has status ERR_CANDIDATE_LIMIT and an empty list."""
+        s, soff = _seed_lists(seeds_per_query)
+        b = soff.size - 1
+        dirs, offs, labs = _path_hops(hops)
+        mask = None if node_mask is None else np.ascontiguousarray(node_mask, dtype=np.uint64)
+        if mask is not None and mask.size != (self.n + 63) // 64:
+            raise HelixDbError(ERR_INVARIANT, f"the node mask holds {mask.size} words, the graph {(self.n + 63) // 64}")
+        ids = np.zeros((max(b, 1), max(int(max_frontier), 1)), np.uint64)
+        lens = np.zeros(max(b, 1), np.uint32); st = np.zeros(max(b, 1), np.uint32)
+        sizes_flat = np.zeros(max(b, 1) * max(dirs.size, 1), np.uint64)
+        _check(lib().hvx_expand_path_lists(self._h, b, _ptr(s), _ptr(soff), dirs.size, _ptr(dirs), _ptr(offs), _ptr(labs), _ptr(mask),
+                                           int(max_frontier), _ptr(ids), _ptr(lens), _ptr(st), _ptr(sizes_flat)))
+        sizes = sizes_flat[: b * dirs.size].reshape(b, dirs.size)
+        return [ids[q, : lens[q]].copy() for q in range(b)], st[:b], sizes
+
+
+def _seed_lists(seeds_per_query):
+    """one id sequence per query -> the C ABI's flat u64 seeds and [b + 1] u64 offsets"""
+    lists = [np.ascontiguousarray(x, dtype=np.uint64).reshape(-1) for x in seeds_per_query]
+    soff = np.zeros(len(lists) + 1, np.uint64)
+    if lists:
+        soff[1:] = np.cumsum([x.size for x in lists], dtype=np.uint64)
+    flat = np.concatenate(lists) if lists else np.zeros(0, np.uint64)
+    return (flat if flat.size else np.zeros(1, np.uint64)), soff
 
 
 def _path_hops(hops):

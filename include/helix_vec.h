@@ -554,6 +554,38 @@ int hvx_prefilter_path_search_batch_params(const hvx_index *, const hvx_csr *, c
                                            uint64_t *out_candidates /*nullable*/, uint64_t *out_hop_sizes /*[n_hops] nullable*/,
                                            hvx_restricted_stats *out_restricted_stats /*[b] nullable*/, hvx_stats *stats);
 
+/* The chain for a BATCH of requests that share the plan (hops, labels, Filter step) and bring their own start nodes: query q starts from
+ * seeds[seed_offsets[q] .. seed_offsets[q+1]).  One launch, one workgroup per query; semantics per query are hvx_expand_path_filter's.
+ * max_frontier (1 .. 16 384) bounds every set of a query's chain, seeds included.  out_ids[q * max_frontier ..) receives the out_lens[q] ids
+ * of F(n_hops) AND node_mask (NULL = keep all) in no particular order, without duplicates.  out_hop_sizes[q * n_hops + i] = |F(i+1)|, unmasked.
+ * A query whose set outgrows max_frontier at hop i: out_status[q] = HVX_ERR_CANDIDATE_LIMIT, out_lens[q] = 0, hop i's size reported as
+ * max_frontier + 1 and later ones as 0; the other queries are unaffected and the call returns HVX_OK.  A query without seeds: length 0, HVX_OK.
+ * Refused before anything runs: HVX_ERR_INVARIANT for a null required argument, n_hops outside 1 .. 16, a bad direction, descending label or
+ * seed offsets, an unknown seed, a query with more than max_frontier seeds; HVX_ERR_UNSUPPORTED for max_frontier 0 or above 16 384 (larger
+ * sets: the shared-seed calls above) and for more than 65 535 queries. */
+int hvx_expand_path_lists(const hvx_csr *, uint32_t b, const uint64_t *seeds, const uint64_t *seed_offsets /*[b+1]*/, uint32_t n_hops,
+                          const uint32_t *hop_direction /*[n_hops]*/, const uint32_t *hop_label_offsets /*[n_hops+1] or NULL*/,
+                          const uint32_t *hop_labels, const uint64_t *node_mask_words /*nullable*/, uint32_t max_frontier,
+                          uint64_t *out_ids /*[b][max_frontier]*/, uint32_t *out_lens /*[b]*/, uint32_t *out_status /*[b]*/,
+                          uint64_t *out_hop_sizes /*[b][n_hops] nullable*/);
+
+/* ... then restricted kNN of query q over ITS set, exactly (the one-launch scan of hvx_search_restricted_lists_device): the chain kernel,
+ * query staging and validation and the scan are enqueued on the index's stream behind ONE host wait; hvx_index_last_scan_path reports
+ * HVX_PATH_DIRECT.  Returns HVX_OK and reports per query: out_status[q] = HVX_ERR_CANDIDATE_LIMIT (count 0) for a chain that outgrew
+ * max_frontier -- whatever the query vector is --, else the validation status of the query vector, else HVX_OK; out_counts[q] = min(k, ids
+ * of the masked set that hold a live vector); out_candidates[q] = the masked set's size, vectorless ids included (0 after an overflow).
+ * A query whose masked set is empty answers nothing with HVX_OK before its vector is validated (restricted.rs:539-541).
+ * Refused before anything runs: what hvx_expand_path_lists refuses, index and graph on different devices (HVX_ERR_INVARIANT); k == 0 or
+ * ef < k (HVX_ERR_K_RANGE); b > max_batch, strategy FILTERED / REFERENCE_PLAN, explicit budgets, an AUTO plan that is not exact for
+ * max_frontier ids, an image the one-launch scan does not serve -- fp8 rows, k > 800 (HVX_ERR_UNSUPPORTED). */
+int hvx_prefilter_path_search_lists_params(const hvx_index *, const hvx_csr *, const float *queries, uint32_t b,
+                                           const hvx_restricted_params *params, const uint64_t *seeds, const uint64_t *seed_offsets /*[b+1]*/,
+                                           uint32_t n_hops, const uint32_t *hop_direction, const uint32_t *hop_label_offsets,
+                                           const uint32_t *hop_labels, const uint64_t *node_mask_words /*nullable*/, uint32_t max_frontier,
+                                           uint64_t *out_ids /*[b][k]*/, float *out_scores, uint32_t *out_counts, uint32_t *out_status /*[b], required*/,
+                                           uint64_t *out_candidates /*[b] nullable*/, uint64_t *out_hop_sizes /*[b][n_hops] nullable*/,
+                                           hvx_stats *stats);
+
 /*
  * Batching operator: the reference calls ValidatedVectorReadIndex::search once per operator invocation
  * from many tokio tasks (access/search/storage.rs:140-163).  Concurrent single-query callers are coalesced into ONE
