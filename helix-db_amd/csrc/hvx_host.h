@@ -335,6 +335,22 @@ struct PathListsArgs {
     uint32_t *lens, *status, *hop_sizes;              // [b] ids in the slot, [b] HVX_OK / HVX_ERR_CANDIDATE_LIMIT, [b][16] |F(i + 1)|
 };
 hipError_t launch_path_lists(const PathListsArgs &args, uint32_t b, hipStream_t s);
+// The batched repeat kernel (hvx_prefilter_repeat.hip): one workgroup per query runs repeat(expand).times(n).emit() from the query's seeds.
+struct RepeatListsArgs {
+    const uint64_t *out_off, *in_off;                 // the CSR, both adjacencies
+    const uint32_t *out_tgt, *in_tgt, *out_lab, *in_lab;
+    const uint32_t *seeds, *seed_off;                 // pinned host memory: every query's seeds back to back, [b + 1] offsets into them
+    uint32_t times, emit, direction, n_allowed;       // the plan the batch shares: 1 .. 16 iterations, HVX_REPEAT_EMIT_*, the body's hop
+    const uint32_t *allowed;                          // the body's label allow-set (n_allowed == 0: every label)
+    const uint32_t *until;                            // nullable: the `until` predicate's node bitmap
+    const uint32_t *mask;                             // nullable: the Filter step's node mask (bitmap words)
+    uint32_t max_frontier;                            // nodes the reach set may hold = ids per slot, at most 16 384
+    uint32_t slots, hash_shift;                       // (filled in by launch_repeat_lists)
+    uint32_t *front;                                  // [b][2][max_frontier] the level lists
+    unsigned long long *out_ids;                      // [b][max_frontier] emitted AND mask, as the scan's external ids
+    uint32_t *lens, *status, *emit_sizes, *stop_depth; // [b] ids in the slot, [b] HVX_OK / HVX_ERR_CANDIDATE_LIMIT, [b][16] |emitted|, [b]
+};
+hipError_t launch_repeat_lists(const RepeatListsArgs &args, uint32_t b, hipStream_t s);
 hipError_t launch_stage_ids(const uint64_t *src, const uint32_t *lens, uint32_t stride, uint64_t *dst, uint32_t b, hipStream_t s);
 // exact tail of the small-batch matrix-core scan (hvx_flat_tail.hip): k <= 64, AVX+FMA tree, L2 / cosine, f32 or bf16 rows
 bool flat_tail_supported(const hvx_index *ix, uint32_t b, uint32_t k, uint32_t n_rows);

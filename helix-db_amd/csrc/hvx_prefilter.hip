@@ -62,6 +62,10 @@ struct hvx_csr {
     // [b][max_frontier] u64 scan slots | [b][2][max_frontier] u32 frontier lists | [b] lengths | [b] statuses | [b][16] hop sizes
     void *lists_buf = nullptr;
     size_t lists_cap = 0;
+    // repeat(expand) with per-query seeds (hvx_expand_repeat_lists / hvx_prefilter_repeat_search_lists_params) shares lists_buf -- its
+    // control words are [b] lengths | [b] statuses | [b][16] emitted sizes | [b] stop depths -- and adds the `until` predicate's bitmap:
+    uint32_t *until_dev = nullptr;                  // [words]
+    uint32_t *h_until = nullptr;                    // pinned staging of it
 };
 
 namespace {
@@ -163,6 +167,7 @@ void csr_free(hvx_csr *g) {
     for (void *p : g->allocs) (void)hipFree(p);
     if (g->h_seeds) (void)hipHostFree(g->h_seeds);
     if (g->h_mask) (void)hipHostFree(g->h_mask);
+    if (g->h_until) (void)hipHostFree(g->h_until);
     if (g->h_hops) (void)hipHostFree(g->h_hops);
     if (g->done) (void)hipEventDestroy(g->done);
     if (g->stream) (void)hipStreamDestroy(g->stream);
@@ -1751,11 +1756,8 @@ int lists_check(const hvx_csr *g, uint32_t b, const uint64_t *seeds, const uint6
 
 struct ListsView { uint64_t *ids; uint32_t *front, *ctl; size_t ctl_words; }; // ctl = [b] lengths | [b] statuses | [b][16] hop sizes
 
-// caller holds g->mu; b != 0.  Seeds and offsets into the pinned buffer, labels and mask uploads and the chain kernel enqueued on `s`.
-int lists_enqueue(hvx_csr *g, hipStream_t s, uint32_t b, const uint64_t *seeds, const uint64_t *seed_offsets, const PathPlan &p,
-                  const uint64_t *node_mask_words, uint32_t max_frontier, ListsView *view) {
-    HIP_TRY(hipSetDevice(g->device));
-    int rc;
+// caller holds g->mu; b != 0.  Every query's seeds and the [b + 1] offsets into them, as u32, in the pinned buffer a kernel reads them from.
+int lists_stage_seeds(hvx_csr *g, hipStream_t s, uint32_t b, const uint64_t *seeds, const uint64_t *seed_offsets, uint32_t **h_off, uint32_t **h_seed) {
     const uint64_t first = seed_offsets[0], total = seed_offsets[b] - first;
     const size_t want = (size_t)b + 1 + total;
     if (want > g->cap_h_seeds) {
@@ -1768,31 +1770,52 @@ int lists_enqueue(hvx_csr *g, hipStream_t s, uint32_t b, const uint64_t *seeds, 
         if (hipHostMalloc((void **)&g->h_seeds, cap * 4, hipHostMallocDefault) != hipSuccess) return fail(HVX_ERR_DEVICE, "hipHostMalloc(%zu) seeds", cap * 4);
         g->cap_h_seeds = cap;
     }
-    uint32_t *h_off = g->h_seeds, *h_seed = g->h_seeds + b + 1;
-    for (uint32_t q = 0; q <= b; ++q) h_off[q] = (uint32_t)(seed_offsets[q] - first);
-    for (uint64_t i = 0; i < total; ++i) h_seed[i] = (uint32_t)seeds[first + i]; // (lists_check has seen every one below n)
-    if ((rc = upload_labels(g, p.labels, p.n_labels, s))) return rc;
-    if (node_mask_words) {
-        const size_t words32 = std::max<size_t>(((g->n + 63) / 64) * 2, 2);
-        if (!g->mask_dev && (rc = csr_alloc(g, (void **)&g->mask_dev, words32 * 4))) return rc;
-        if (!g->h_mask && hipHostMalloc((void **)&g->h_mask, words32 * 4, hipHostMallocDefault) != hipSuccess)
-            return fail(HVX_ERR_DEVICE, "hipHostMalloc(%zu) mask", words32 * 4);
-        memcpy(g->h_mask, node_mask_words, (size_t)((g->n + 63) / 64) * 8);
-        HIP_TRY(hipMemcpyAsync(g->mask_dev, g->h_mask, (size_t)((g->n + 63) / 64) * 8, hipMemcpyHostToDevice, s));
+    *h_off = g->h_seeds;
+    *h_seed = g->h_seeds + b + 1;
+    for (uint32_t q = 0; q <= b; ++q) (*h_off)[q] = (uint32_t)(seed_offsets[q] - first);
+    for (uint64_t i = 0; i < total; ++i) (*h_seed)[i] = (uint32_t)seeds[first + i]; // (the argument check has seen every one below n)
+    return HVX_OK;
+}
+
+// a node bitmap (the Filter step's mask, repeat's `until` predicate) through its pinned staging buffer into its device buffer, on `s`
+int lists_stage_bitmap(hvx_csr *g, hipStream_t s, const uint64_t *words, uint32_t **dev, uint32_t **pinned) {
+    const size_t words32 = std::max<size_t>(((g->n + 63) / 64) * 2, 2), bytes = (size_t)((g->n + 63) / 64) * 8;
+    int rc;
+    if (!*dev && (rc = csr_alloc(g, (void **)dev, words32 * 4))) return rc;
+    if (!*pinned && hipHostMalloc((void **)pinned, words32 * 4, hipHostMallocDefault) != hipSuccess)
+        return fail(HVX_ERR_DEVICE, "hipHostMalloc(%zu) mask", words32 * 4);
+    memcpy(*pinned, words, bytes);
+    HIP_TRY(hipMemcpyAsync(*dev, *pinned, bytes, hipMemcpyHostToDevice, s));
+    return HVX_OK;
+}
+
+// g->lists_buf of at least `bytes` (every call that used the old one has waited for its stream)
+int lists_reserve(hvx_csr *g, size_t bytes) {
+    if (bytes <= g->lists_cap) return HVX_OK;
+    if (g->lists_buf) {
+        g->allocs.erase(std::remove(g->allocs.begin(), g->allocs.end(), g->lists_buf), g->allocs.end());
+        (void)hipFree(g->lists_buf);
+        g->lists_buf = nullptr;
+        g->lists_cap = 0;
     }
+    int rc = csr_alloc(g, &g->lists_buf, bytes);
+    if (rc) return rc;
+    g->lists_cap = bytes;
+    return HVX_OK;
+}
+
+// caller holds g->mu; b != 0.  Seeds and offsets into the pinned buffer, labels and mask uploads and the chain kernel enqueued on `s`.
+int lists_enqueue(hvx_csr *g, hipStream_t s, uint32_t b, const uint64_t *seeds, const uint64_t *seed_offsets, const PathPlan &p,
+                  const uint64_t *node_mask_words, uint32_t max_frontier, ListsView *view) {
+    HIP_TRY(hipSetDevice(g->device));
+    int rc;
+    uint32_t *h_off, *h_seed;
+    if ((rc = lists_stage_seeds(g, s, b, seeds, seed_offsets, &h_off, &h_seed))) return rc;
+    if ((rc = upload_labels(g, p.labels, p.n_labels, s))) return rc;
+    if (node_mask_words && (rc = lists_stage_bitmap(g, s, node_mask_words, &g->mask_dev, &g->h_mask))) return rc;
     const size_t slots = (size_t)b * max_frontier;
     view->ctl_words = (size_t)b * (2 + kMaxPathHops);
-    const size_t bytes = slots * 8 + slots * 2 * 4 + view->ctl_words * 4;
-    if (bytes > g->lists_cap) {
-        if (g->lists_buf) { // (every call that used it has waited for its stream)
-            g->allocs.erase(std::remove(g->allocs.begin(), g->allocs.end(), g->lists_buf), g->allocs.end());
-            (void)hipFree(g->lists_buf);
-            g->lists_buf = nullptr;
-            g->lists_cap = 0;
-        }
-        if ((rc = csr_alloc(g, &g->lists_buf, bytes))) return rc;
-        g->lists_cap = bytes;
-    }
+    if ((rc = lists_reserve(g, slots * 8 + slots * 2 * 4 + view->ctl_words * 4))) return rc;
     view->ids = static_cast<uint64_t *>(g->lists_buf);
     view->front = reinterpret_cast<uint32_t *>(view->ids + slots);
     view->ctl = view->front + slots * 2;
@@ -1893,5 +1916,148 @@ extern "C" int hvx_prefilter_path_search_lists_params(const hvx_index *cix, cons
         }
     }
     lists_sizes_out(ctl, b, n_hops, out_hop_sizes);
+    return HVX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// repeat(expand).times(n).emit() with per-query seeds (control/repeat.rs:24-99): the same loop (body hop, times, emit mode, `until`
+// predicate, Filter step) for every request of a batch, each request from its own start nodes.  One launch of repeat_lists_kernel
+// (hvx_prefilter_repeat.hip) runs every loop and leaves query q's emitted set in slot q of the one-launch scan.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+// the argument rules of both entry points: nothing is enqueued, nothing of the graph is touched
+int repeat_check(const hvx_csr *g, uint32_t b, const uint64_t *seeds, const uint64_t *seed_offsets, uint32_t times, uint32_t emit, uint32_t direction,
+                 const uint32_t *allowed_label_ids, uint32_t n_labels, uint32_t max_frontier) {
+    if (times == 0 || times > kMaxPathHops) return fail(HVX_ERR_INVARIANT, "repeat runs 1 .. %u times, not %u", kMaxPathHops, times);
+    if (emit < HVX_REPEAT_EMIT_BEFORE || emit > HVX_REPEAT_EMIT_ALL)
+        return fail(HVX_ERR_INVARIANT, "emit mode %u: BEFORE, AFTER or ALL (emit None is the chain of hvx_expand_path_lists)", emit);
+    if (n_labels && !allowed_label_ids) return fail(HVX_ERR_INVARIANT, "null labels");
+    PathPlan body; // the seed and slot rules are the chain's, over a plan of the one body hop
+    return lists_check(g, b, seeds, seed_offsets, 1, &direction, nullptr, nullptr, max_frontier, &body);
+}
+
+struct RepeatView { uint64_t *ids; uint32_t *ctl; size_t ctl_words; }; // ctl = [b] lengths | [b] statuses | [b][16] emitted sizes | [b] stop depths
+
+// caller holds g->mu; b != 0.  Seeds and offsets into the pinned buffer, label and bitmap uploads and the repeat kernel enqueued on `s`.
+int repeat_enqueue(hvx_csr *g, hipStream_t s, uint32_t b, const uint64_t *seeds, const uint64_t *seed_offsets, uint32_t times, uint32_t emit,
+                   uint32_t direction, const uint32_t *allowed_label_ids, uint32_t n_labels, const uint64_t *until_mask_words,
+                   const uint64_t *node_mask_words, uint32_t max_frontier, RepeatView *view) {
+    HIP_TRY(hipSetDevice(g->device));
+    int rc;
+    uint32_t *h_off, *h_seed;
+    if ((rc = lists_stage_seeds(g, s, b, seeds, seed_offsets, &h_off, &h_seed))) return rc;
+    if ((rc = upload_labels(g, allowed_label_ids, n_labels, s))) return rc;
+    if (until_mask_words && (rc = lists_stage_bitmap(g, s, until_mask_words, &g->until_dev, &g->h_until))) return rc;
+    if (node_mask_words && (rc = lists_stage_bitmap(g, s, node_mask_words, &g->mask_dev, &g->h_mask))) return rc;
+    // the chain's buffer (scan slots | level lists | control words), with one more control word per query
+    const size_t slots = (size_t)b * max_frontier;
+    view->ctl_words = (size_t)b * (3 + kMaxPathHops);
+    if ((rc = lists_reserve(g, slots * 8 + slots * 2 * 4 + view->ctl_words * 4))) return rc;
+    view->ids = static_cast<uint64_t *>(g->lists_buf);
+    uint32_t *front = reinterpret_cast<uint32_t *>(view->ids + slots);
+    view->ctl = front + slots * 2;
+    RepeatListsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.out_off = g->out_off; a.in_off = g->in_off;
+    a.out_tgt = g->out_tgt; a.in_tgt = g->in_tgt; a.out_lab = g->out_lab; a.in_lab = g->in_lab;
+    a.seeds = h_seed; a.seed_off = h_off;
+    a.times = times; a.emit = emit; a.direction = direction; a.n_allowed = n_labels;
+    a.allowed = g->labels;
+    a.until = until_mask_words ? g->until_dev : nullptr;
+    a.mask = node_mask_words ? g->mask_dev : nullptr;
+    a.max_frontier = max_frontier;
+    a.front = front;
+    a.out_ids = reinterpret_cast<unsigned long long *>(view->ids);
+    a.lens = view->ctl; a.status = view->ctl + b; a.emit_sizes = view->ctl + 2 * (size_t)b;
+    a.stop_depth = view->ctl + (2 + kMaxPathHops) * (size_t)b;
+    HIP_TRY(launch_repeat_lists(a, b, s));
+    return HVX_OK;
+}
+
+void repeat_ctl_out(const uint32_t *ctl, uint32_t b, uint32_t times, uint32_t *out_stop_depth, uint64_t *out_emit_sizes) {
+    for (uint32_t q = 0; q < b; ++q) {
+        if (out_stop_depth) out_stop_depth[q] = ctl[(2 + kMaxPathHops) * (size_t)b + q];
+        if (out_emit_sizes)
+            for (uint32_t i = 0; i < times; ++i) out_emit_sizes[(size_t)q * times + i] = ctl[2 * (size_t)b + (size_t)q * kMaxPathHops + i];
+    }
+}
+
+} // namespace
+
+extern "C" int hvx_expand_repeat_lists(const hvx_csr *cg, uint32_t b, const uint64_t *seeds, const uint64_t *seed_offsets, uint32_t times,
+                                       uint32_t emit, uint32_t direction, const uint32_t *allowed_label_ids, uint32_t n_labels,
+                                       const uint64_t *until_mask_words, const uint64_t *node_mask_words, uint32_t max_frontier,
+                                       uint64_t *out_ids, uint32_t *out_lens, uint32_t *out_status, uint32_t *out_stop_depth,
+                                       uint64_t *out_emit_sizes) {
+    if (!cg || !out_ids || !out_lens || !out_status) return fail(HVX_ERR_INVARIANT, "null argument");
+    hvx_csr *g = const_cast<hvx_csr *>(cg);
+    int rc = repeat_check(g, b, seeds, seed_offsets, times, emit, direction, allowed_label_ids, n_labels, max_frontier);
+    if (rc) return rc;
+    if (b == 0) return HVX_OK;
+    std::lock_guard<std::mutex> lock(g->mu);
+    RepeatView v;
+    if ((rc = repeat_enqueue(g, g->stream, b, seeds, seed_offsets, times, emit, direction, allowed_label_ids, n_labels, until_mask_words,
+                             node_mask_words, max_frontier, &v))) {
+        (void)hipStreamSynchronize(g->stream);
+        return rc;
+    }
+    std::vector<uint32_t> ctl(v.ctl_words);
+    HIP_TRY(hipMemcpyAsync(ctl.data(), v.ctl, v.ctl_words * 4, hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipMemcpyAsync(out_ids, v.ids, (size_t)b * max_frontier * 8, hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    for (uint32_t q = 0; q < b; ++q) { out_lens[q] = ctl[q]; out_status[q] = ctl[b + q]; }
+    repeat_ctl_out(ctl.data(), b, times, out_stop_depth, out_emit_sizes);
+    return HVX_OK;
+}
+
+extern "C" int hvx_prefilter_repeat_search_lists_params(const hvx_index *cix, const hvx_csr *cg, const float *queries, uint32_t b,
+                                                        const hvx_restricted_params *params, const uint64_t *seeds, const uint64_t *seed_offsets,
+                                                        uint32_t times, uint32_t emit, uint32_t direction, const uint32_t *allowed_label_ids,
+                                                        uint32_t n_labels, const uint64_t *until_mask_words, const uint64_t *node_mask_words,
+                                                        uint32_t max_frontier, uint64_t *out_ids, float *out_scores, uint32_t *out_counts,
+                                                        uint32_t *out_status, uint64_t *out_candidates, uint32_t *out_stop_depth,
+                                                        uint64_t *out_emit_sizes, hvx_stats *stats) {
+    if (!cix || !cg || !params || !out_ids || !out_scores || !out_counts || !out_status || (b && !queries)) return fail(HVX_ERR_INVARIANT, "null argument");
+    if (params->strategy > HVX_RESTRICTED_REFERENCE_PLAN) return fail(HVX_ERR_INVARIANT, "unknown restricted strategy %u", params->strategy);
+    hvx_index *ix = const_cast<hvx_index *>(cix);
+    hvx_csr *g = const_cast<hvx_csr *>(cg);
+    const uint32_t k = params->k;
+    if (k == 0) return fail(HVX_ERR_K_RANGE, "result count must be non-zero");
+    if (params->ef < k) return fail(HVX_ERR_K_RANGE, "search beam width %u is below the result count %u", params->ef, k);
+    if (ix->device != g->device) return fail(HVX_ERR_INVARIANT, "index and graph live on different devices");
+    int rc = repeat_check(g, b, seeds, seed_offsets, times, emit, direction, allowed_label_ids, n_labels, max_frontier);
+    if (rc) return rc;
+    if (b > ix->max_batch) return fail(HVX_ERR_UNSUPPORTED, "batch %u exceeds max_batch %u given at import", b, ix->max_batch);
+    std::lock_guard<std::mutex> glock(g->mu);
+    std::lock_guard<std::mutex> lock(ix->mu);
+    ix->sync_rewrites();
+    // this call IS the exact scan (as hvx_prefilter_path_search_lists_params): a plan that would walk a set of max_frontier ids is not served
+    RestrictedPlan plan;
+    if (params->strategy == HVX_RESTRICTED_FILTERED || params->strategy == HVX_RESTRICTED_REFERENCE_PLAN || params->explicit_budgets ||
+        restricted_make_plan(*params, max_frontier, ix->dev.dim, &plan, ix) != HVX_OK || plan.strategy != HVX_RESTRICTED_EXACT)
+        return fail(HVX_ERR_UNSUPPORTED, "per-query repeats are answered by the exact scan: strategy EXACT, or AUTO with max_frontier x row bytes within the "
+                    "device plan's limit, and no explicit budgets");
+    if (!restricted_direct_supported(ix, k))
+        return fail(HVX_ERR_UNSUPPORTED, "the one-launch restricted scan serves k <= 800 over f32 / bf16 rows of a non-empty image");
+    if (b == 0) return HVX_OK;
+    hipStream_t s = ix->stream;
+    RepeatView v;
+    if ((rc = repeat_enqueue(g, s, b, seeds, seed_offsets, times, emit, direction, allowed_label_ids, n_labels, until_mask_words, node_mask_words,
+                             max_frontier, &v)) ||
+        (rc = restricted_direct_lists_devlens(ix, queries, b, k, v.ids, max_frontier, v.ctl, v.ctl_words, out_ids, out_scores, out_counts,
+                                              out_status, stats))) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    const uint32_t *ctl = ix->h_flags;
+    for (uint32_t q = 0; q < b; ++q) {
+        if (out_candidates) out_candidates[q] = ctl[q];
+        if (ctl[b + q] != HVX_OK) { // the reach set outgrew its slot: this wins over what the scan made of the query vector
+            out_status[q] = ctl[b + q];
+            out_counts[q] = 0;
+        }
+    }
+    repeat_ctl_out(ctl, b, times, out_stop_depth, out_emit_sizes);
     return HVX_OK;
 }

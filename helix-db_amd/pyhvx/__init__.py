@@ -25,6 +25,7 @@ KERNEL_SCALAR, KERNEL_SSE, KERNEL_AVX, KERNEL_AVX_FMA, KERNEL_NEON = 0, 1, 2, 3,
 OK, ERR_DIMENSION, ERR_NONFINITE, ERR_ZERO_NORM, ERR_MAGNITUDE, ERR_K_RANGE, ERR_CANDIDATE_LIMIT, \
     ERR_DEVICE, ERR_INVARIANT, ERR_UNSUPPORTED, PENDING, ERR_BUSY, ERR_TIMEOUT = range(13)
 DIR_OUT, DIR_IN, DIR_BOTH = 0, 1, 2
+REPEAT_EMIT_BEFORE, REPEAT_EMIT_AFTER, REPEAT_EMIT_ALL = 1, 2, 3  # repeat(..).emit() modes (HVX_REPEAT_EMIT_*; emit None is a plain chain)
 
 _STATUS_NAMES = {
     1: "InvalidDimension", 2: "InvalidVectorComponent", 3: "ZeroNormCosineVector",
@@ -369,6 +370,13 @@ def lib():
     L.hvx_prefilter_path_search_lists_params.restype = C.c_int
     L.hvx_prefilter_path_search_lists_params.argtypes = [_vp, _vp, _vp, C.c_uint32, C.POINTER(RestrictedParams), _vp, _vp, C.c_uint32, _vp, _vp, _vp,
                                                          _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(Stats)]
+    L.hvx_expand_repeat_lists.restype = C.c_int
+    L.hvx_expand_repeat_lists.argtypes = [_vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, _vp, C.c_uint32,
+                                          _vp, _vp, _vp, _vp, _vp]
+    L.hvx_prefilter_repeat_search_lists_params.restype = C.c_int
+    L.hvx_prefilter_repeat_search_lists_params.argtypes = [_vp, _vp, _vp, C.c_uint32, C.POINTER(RestrictedParams), _vp, _vp, C.c_uint32, C.c_uint32,
+                                                           C.c_uint32, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                           C.POINTER(Stats)]
     L.hvx_batcher_new.restype = C.c_int
     L.hvx_batcher_new.argtypes = [_vp, C.POINTER(_Params), C.c_uint32, C.c_uint32, C.POINTER(_vp)]
     L.hvx_batcher_free.argtypes = [_vp]
@@ -977,6 +985,33 @@ class ValidatedVectorReadIndex:
         out = (ids, sc, cnt, st, ncand, stats.as_dict())
         return out + (sizes[:, : dirs.size],) if want_sizes else out
 
+    def prefilter_repeat_search_lists(self, graph: "Graph", queries, params, seeds_per_query, times, emit, direction=DIR_OUT, allowed_labels=(),
+                                      until_mask=None, node_mask=None, max_frontier=4096, want_sizes=False):
+        """repeat(expand).times(times).emit() for a batch of requests that share the loop and bring their OWN start nodes, then the exact
+        scan of every query over its own emitted set, in one call (hvx_prefilter_repeat_search_lists_params).  `params`: SearchParams (the
+        exact scan) or RestrictedParams; `emit`: REPEAT_EMIT_BEFORE / AFTER / ALL; `max_frontier` (<= 16 384) bounds a request's reach set.
+        Returns (ids, scores, counts, statuses, n_candidates per query, stats) (+ [b] stop depths and [b][times] emitted sizes, unmasked,
+        when want_sizes).  A query whose reach set outgrew max_frontier has status ERR_CANDIDATE_LIMIT and count 0; the call itself raises
+        only when refused."""
+        q = self._q(queries)
+        rp = params if isinstance(params, RestrictedParams) else RestrictedParams(k=params.k, ef=params.ef, strategy=RESTRICTED_EXACT)
+        b, k = q.shape[0], int(rp.k)
+        s, soff = _seed_lists(seeds_per_query)
+        if soff.size != b + 1:
+            raise HelixDbError(ERR_INVARIANT, f"{soff.size - 1} seed lists for {b} queries")
+        lab = np.ascontiguousarray(list(allowed_labels), dtype=np.uint32)
+        until, mask = _node_bitmap(until_mask, graph.n, "until"), _node_bitmap(node_mask, graph.n, "node")
+        ids = np.zeros((b, k), np.uint64); sc = np.zeros((b, k), np.float32); cnt = np.zeros(b, np.uint32); st = np.zeros(b, np.uint32)
+        ncand = np.zeros(b, np.uint64); stop = np.zeros(b, np.uint32)
+        sizes = np.zeros((b, max(int(times), 1)), np.uint64)
+        stats = Stats()
+        _check(lib().hvx_prefilter_repeat_search_lists_params(self._h, graph._h, _ptr(q), b, C.byref(rp), _ptr(s), _ptr(soff), int(times), int(emit),
+                                                              int(direction), _ptr(lab), lab.size, _ptr(until), _ptr(mask), int(max_frontier),
+                                                              _ptr(ids), _ptr(sc), _ptr(cnt), _ptr(st), _ptr(ncand), _ptr(stop), _ptr(sizes),
+                                                              C.byref(stats)))
+        out = (ids, sc, cnt, st, ncand, stats.as_dict())
+        return out + (stop, sizes[:, : int(times)]) if want_sizes else out
+
     # ---- device-resident surface (torch tensors on the index's GPU) ----
     def search_batch_device(self, d_queries, k, ef, d_ids, d_scores, d_counts, d_status, d_qstats=None, want_stats=False):
         stats = Stats()
@@ -1414,6 +1449,34 @@ class Graph:
         sizes = sizes_flat[: b * dirs.size].reshape(b, dirs.size)
         return [ids[q, : lens[q]].copy() for q in range(b)], st[:b], sizes
 
+    def expand_repeat_lists(self, seeds_per_query, times, emit, direction=DIR_OUT, allowed_labels=(), until_mask=None, node_mask=None,
+                            max_frontier=4096):
+        """repeat(expand).times(times).emit() for a batch of queries that share the loop and start from their OWN seeds
+        (hvx_expand_repeat_lists).  `emit`: REPEAT_EMIT_BEFORE / AFTER / ALL; `until_mask` / `node_mask`: node bitmap words or None.
+        Returns ([ids of query q's emitted set AND node_mask, in no particular order], statuses, [b] stop depths, [b][times] emitted
+        sizes, unmasked).  A query whose reach set outgrew max_frontier (<= 16 384) has status ERR_CANDIDATE_LIMIT and an empty list."""
+        s, soff = _seed_lists(seeds_per_query)
+        b = soff.size - 1
+        lab = np.ascontiguousarray(list(allowed_labels), dtype=np.uint32)
+        until, mask = _node_bitmap(until_mask, self.n, "until"), _node_bitmap(node_mask, self.n, "node")
+        ids = np.zeros((max(b, 1), max(int(max_frontier), 1)), np.uint64)
+        lens = np.zeros(max(b, 1), np.uint32); st = np.zeros(max(b, 1), np.uint32); stop = np.zeros(max(b, 1), np.uint32)
+        sizes_flat = np.zeros(max(b, 1) * max(int(times), 1), np.uint64)
+        _check(lib().hvx_expand_repeat_lists(self._h, b, _ptr(s), _ptr(soff), int(times), int(emit), int(direction), _ptr(lab), lab.size,
+                                             _ptr(until), _ptr(mask), int(max_frontier), _ptr(ids), _ptr(lens), _ptr(st), _ptr(stop),
+                                             _ptr(sizes_flat)))
+        sizes = sizes_flat[: b * int(times)].reshape(b, int(times))
+        return [ids[q, : lens[q]].copy() for q in range(b)], st[:b], stop[:b], sizes
+
+
+def _node_bitmap(words, n, what):
+    """a node bitmap argument (None passes through) as the C ABI's u64 words, its length checked against the graph"""
+    if words is None:
+        return None
+    w = np.ascontiguousarray(words, dtype=np.uint64)
+    if w.size != (n + 63) // 64:
+        raise HelixDbError(ERR_INVARIANT, f"the {what} mask holds {w.size} words, the graph {(n + 63) // 64}")
+    return w
 
 def _seed_lists(seeds_per_query):
     """one id sequence per query -> the C ABI's flat u64 seeds and [b + 1] u64 offsets"""

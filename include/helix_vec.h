@@ -586,6 +586,47 @@ int hvx_prefilter_path_search_lists_params(const hvx_index *, const hvx_csr *, c
                                            uint64_t *out_candidates /*[b] nullable*/, uint64_t *out_hop_sizes /*[b][n_hops] nullable*/,
                                            hvx_stats *stats);
 
+/* repeat(expand).times(n).emit() for a BATCH of requests that share the plan and bring their own start nodes (control/repeat.rs:24-99),
+ * on sets.  The body is ONE expand hop (direction, label allow-set: n_labels == 0 means every label).  Per request:
+ *   cur = the distinct seeds; emitted = {}
+ *   for i in 1 .. times:  BEFORE / ALL: emitted |= cur;  nxt = union of the body's neighbours of cur (no visited exclusion, a node without
+ *     arcs drops out);  AFTER / ALL: emitted |= nxt;  stop = until_mask given and nxt holds one of its nodes (the seeds never stop the loop);
+ *     cur = nxt;  if cur is empty or stop: break
+ * out_ids[q * max_frontier ..) receives the out_lens[q] ids of emitted AND node_mask (NULL = keep all), in no particular order, without
+ * duplicates.  out_emit_sizes[q * times + i] = |emitted| (unmasked) after iteration i + 1, or at the loop's end when it ended sooner.
+ * out_stop_depth[q] = the 1-based iteration at which `until` fired, 0 if it never did.
+ * max_frontier (1 .. 16 384) bounds the REACH set: the seeds (counted for BEFORE and ALL) and every node an iteration reached.  Under
+ * BEFORE the last level reached counts although it is not emitted, so a request may overflow whose emitted set would have fit.
+ * A request whose reach set outgrows max_frontier at iteration i: out_status[q] = HVX_ERR_CANDIDATE_LIMIT, out_lens[q] = 0, iteration
+ * i's size reported as max_frontier + 1 and later ones as 0, stop depth 0 (overflow wins over an `until` hit of the same iteration); the
+ * other requests are unaffected and the call returns HVX_OK.  A request without seeds: length 0, HVX_OK.
+ * Emit `None` is the chain hvx_expand_path_lists with the hop repeated.  AfterIf{predicate} is AFTER with the predicate folded into node_mask.
+ * Refused before anything runs: HVX_ERR_INVARIANT for a null required argument, times outside 1 .. 16, a bad emit or direction, descending
+ * seed offsets, an unknown seed, a request with more than max_frontier seeds; HVX_ERR_UNSUPPORTED for max_frontier 0 or above 16 384 and
+ * for more than 65 535 requests. */
+enum { HVX_REPEAT_EMIT_BEFORE = 1, HVX_REPEAT_EMIT_AFTER = 2, HVX_REPEAT_EMIT_ALL = 3 };
+int hvx_expand_repeat_lists(const hvx_csr *, uint32_t b, const uint64_t *seeds, const uint64_t *seed_offsets /*[b+1]*/, uint32_t times,
+                            uint32_t emit, uint32_t direction, const uint32_t *allowed_label_ids, uint32_t n_labels,
+                            const uint64_t *until_mask_words /*nullable*/, const uint64_t *node_mask_words /*nullable*/, uint32_t max_frontier,
+                            uint64_t *out_ids /*[b][max_frontier]*/, uint32_t *out_lens /*[b]*/, uint32_t *out_status /*[b]*/,
+                            uint32_t *out_stop_depth /*[b] nullable*/, uint64_t *out_emit_sizes /*[b][times] nullable*/);
+
+/* ... then restricted kNN of query q over ITS emitted set, exactly: the repeat kernel, query staging and validation and the one-launch scan
+ * are enqueued on the index's stream behind ONE host wait; hvx_index_last_scan_path reports HVX_PATH_DIRECT.  Per-query statuses, counts and
+ * out_candidates are as for hvx_prefilter_path_search_lists_params: HVX_ERR_CANDIDATE_LIMIT (count 0) first, an empty masked set answers
+ * nothing with HVX_OK before its vector is validated, else the query vector's validation status.
+ * Refused before anything runs: what hvx_expand_repeat_lists refuses, index and graph on different devices (HVX_ERR_INVARIANT); k == 0 or
+ * ef < k (HVX_ERR_K_RANGE); b > max_batch, strategy FILTERED / REFERENCE_PLAN, explicit budgets, an AUTO plan that is not exact for
+ * max_frontier ids, fp8 rows, k > 800 (HVX_ERR_UNSUPPORTED). */
+int hvx_prefilter_repeat_search_lists_params(const hvx_index *, const hvx_csr *, const float *queries, uint32_t b,
+                                             const hvx_restricted_params *params, const uint64_t *seeds, const uint64_t *seed_offsets /*[b+1]*/,
+                                             uint32_t times, uint32_t emit, uint32_t direction, const uint32_t *allowed_label_ids,
+                                             uint32_t n_labels, const uint64_t *until_mask_words /*nullable*/,
+                                             const uint64_t *node_mask_words /*nullable*/, uint32_t max_frontier,
+                                             uint64_t *out_ids /*[b][k]*/, float *out_scores, uint32_t *out_counts, uint32_t *out_status /*[b], required*/,
+                                             uint64_t *out_candidates /*[b] nullable*/, uint32_t *out_stop_depth /*[b] nullable*/,
+                                             uint64_t *out_emit_sizes /*[b][times] nullable*/, hvx_stats *stats);
+
 /*
  * Batching operator: the reference calls ValidatedVectorReadIndex::search once per operator invocation
  * from many tokio tasks (access/search/storage.rs:140-163).  Concurrent single-query callers are coalesced into ONE
