@@ -9,6 +9,7 @@
 #include <mutex>
 #include <vector>
 
+#include "hvx_csr_view.h"
 #include "hvx_kernels.h"
 #include "hvx_walk_core.h"
 
@@ -322,14 +323,13 @@ int restricted_direct_lists_devlens(hvx_index *ix, const float *queries, uint32_
                                     uint32_t *out_status, hvx_stats *stats);
 // The batched chain kernel (hvx_prefilter_batch.hip): one workgroup per query walks the query's own chain of hops.
 struct PathListsArgs {
-    const uint64_t *out_off, *in_off;                 // the CSR, both adjacencies
-    const uint32_t *out_tgt, *in_tgt, *out_lab, *in_lab;
+    CsrView g;                                        // the CSR, both adjacencies
     const uint32_t *seeds, *seed_off;                 // pinned host memory: every query's seeds back to back, [b + 1] offsets into them
     uint32_t n_hops, direction[16], label_off[17];    // the plan the batch shares; hop i's allow-set = labels[label_off[i] .. label_off[i + 1])
     const uint32_t *labels;
     const uint32_t *mask;                             // nullable: the Filter step's node mask (bitmap words)
     uint32_t max_frontier;                            // ids per slot, at most 16 384
-    uint32_t slots, hash_shift;                       // (filled in by launch_path_lists)
+    uint32_t slots, hash_shift;                       // (filled in by launch_node_set_kernel)
     uint32_t *front;                                  // [b][2][max_frontier] the frontier lists
     unsigned long long *out_ids;                      // [b][max_frontier] the final set AND mask, as the scan's external ids
     uint32_t *lens, *status, *hop_sizes;              // [b] ids in the slot, [b] HVX_OK / HVX_ERR_CANDIDATE_LIMIT, [b][16] |F(i + 1)|
@@ -337,15 +337,14 @@ struct PathListsArgs {
 hipError_t launch_path_lists(const PathListsArgs &args, uint32_t b, hipStream_t s);
 // The batched repeat kernel (hvx_prefilter_repeat.hip): one workgroup per query runs repeat(expand).times(n).emit() from the query's seeds.
 struct RepeatListsArgs {
-    const uint64_t *out_off, *in_off;                 // the CSR, both adjacencies
-    const uint32_t *out_tgt, *in_tgt, *out_lab, *in_lab;
+    CsrView g;                                        // the CSR, both adjacencies
     const uint32_t *seeds, *seed_off;                 // pinned host memory: every query's seeds back to back, [b + 1] offsets into them
     uint32_t times, emit, direction, n_allowed;       // the plan the batch shares: 1 .. 16 iterations, HVX_REPEAT_EMIT_*, the body's hop
     const uint32_t *allowed;                          // the body's label allow-set (n_allowed == 0: every label)
     const uint32_t *until;                            // nullable: the `until` predicate's node bitmap
     const uint32_t *mask;                             // nullable: the Filter step's node mask (bitmap words)
     uint32_t max_frontier;                            // nodes the reach set may hold = ids per slot, at most 16 384
-    uint32_t slots, hash_shift;                       // (filled in by launch_repeat_lists)
+    uint32_t slots, hash_shift;                       // (filled in by launch_node_set_kernel)
     uint32_t *front;                                  // [b][2][max_frontier] the level lists
     unsigned long long *out_ids;                      // [b][max_frontier] emitted AND mask, as the scan's external ids
     uint32_t *lens, *status, *emit_sizes, *stop_depth; // [b] ids in the slot, [b] HVX_OK / HVX_ERR_CANDIDATE_LIMIT, [b][16] |emitted|, [b]

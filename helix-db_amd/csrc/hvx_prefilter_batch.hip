@@ -1,5 +1,5 @@
 // hvx_prefilter_batch.hip -- chains of `expand` hops for a BATCH of requests, every request from its own start nodes
-// (hvx_expand_path_lists / hvx_prefilter_path_search_lists_params; the entry points live in hvx_prefilter.hip beside the graph handle).
+// (hvx_expand_path_lists / hvx_prefilter_path_search_lists_params; the entry points live in hvx_prefilter.hip, the graph handle in hvx_csr.h, the row walker and the node set in hvx_csr_dev.h).
 //
 // Reference: one stored query such as g().n(user).out("follows").out("likes").vector_search(..) runs once per request: the compiled plan
 // (hop directions, edge labels, Filter step) is the same, the bind parameters (start nodes) and the query vector are the request's own
@@ -25,48 +25,23 @@
 // + 8 B per frontier node written and read back.  The kernel is latency-bound (dependent offset -> target -> LDS probe chains), not HBM-bound.
 #include <hip/hip_runtime.h>
 
+#include "hvx_csr_dev.h"
 #include "hvx_host.h"
 
 using namespace hvx;
 
 namespace {
 
-constexpr uint32_t kEmpty = 0xFFFFFFFFu;
-constexpr uint32_t kLight = 16;    // rows up to this long are walked by their own lane
-constexpr uint32_t kCtlWords = 32; // LDS words in front of the table: [0] size of the set under construction, [1] ids written by the last hop, [8 ..) hop sizes
-
-__device__ __forceinline__ bool lists_label_ok(uint32_t lab, const uint32_t *allowed, uint32_t n_allowed) {
-    if (n_allowed == 0) return true; // an empty allow-set means every label (traversal.rs:53)
-    for (uint32_t i = 0; i < n_allowed; ++i)
-        if (allowed[i] == lab) return true;
-    return false;
-}
-
+// LDS control words in front of the table: [0] size of the set under construction, [1] ids written by the last hop, [8 ..) hop sizes
 __global__ __launch_bounds__(1024) void path_lists_kernel(PathListsArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint32_t *ctl = reinterpret_cast<uint32_t *>(smem);
-    uint32_t *tab = ctl + kCtlWords;
+    const LdsNodeSet set{ctl + kNodeSetCtlWords, a.slots, a.hash_shift};
     const uint32_t q = blockIdx.x, tid = threadIdx.x, lane = tid & 63u;
-    const uint32_t mf = a.max_frontier, slot_mask = a.slots - 1u;
-    const unsigned long long below = (1ull << lane) - 1ull;
+    const uint32_t mf = a.max_frontier;
+    auto room = [&]() __attribute__((always_inline)) -> bool { return !LdsNodeSet::over(&ctl[0], mf); };
 
-    // test-and-set of v in the table; a full table answers "seen" (only a set past max_frontier gets there: its chain is over)
-    auto insert = [&](uint32_t v) __attribute__((always_inline)) -> bool {
-        uint32_t h = (v * 0x9E3779B1u) >> a.hash_shift;
-        for (uint32_t probe = 0; probe < a.slots; ++probe) {
-            const uint32_t old = atomicCAS(&tab[h], kEmpty, v);
-            if (old == kEmpty) return true;
-            if (old == v) return false;
-            h = (h + 1u) & slot_mask;
-        }
-        return false;
-    };
-    // wave-uniform: the set under construction has outgrown the slot
-    auto over = [&]() __attribute__((always_inline)) -> bool {
-        return (uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(&ctl[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) > mf;
-    };
-
-    if (tid < kCtlWords) ctl[tid] = 0u;
+    if (tid < kNodeSetCtlWords) ctl[tid] = 0u;
     const uint32_t s0 = a.seed_off[q];
     uint32_t n_cur = a.seed_off[q + 1] - s0; // (the host has seen it at most max_frontier)
     const uint32_t *cur = a.seeds + s0;
@@ -76,7 +51,7 @@ __global__ __launch_bounds__(1024) void path_lists_kernel(PathListsArgs a) {
 
     for (uint32_t hop = 0; hop < a.n_hops && n_cur != 0u; ++hop) {
         const bool last = hop + 1u == a.n_hops;
-        for (uint32_t i = tid; i < a.slots; i += 1024u) tab[i] = kEmpty;
+        set.clear(tid);
         if (tid == 0) ctl[0] = 0u;
         __syncthreads();
         uint32_t *dst = slot[hop & 1u];
@@ -87,57 +62,27 @@ __global__ __launch_bounds__(1024) void path_lists_kernel(PathListsArgs a) {
         auto take = [&](bool active, const uint32_t *tgt, const uint32_t *lab, uint64_t at) __attribute__((always_inline)) {
             uint32_t v = 0;
             bool fresh = false;
-            if (active && (!lab || lists_label_ok(lab[at], allowed, n_allowed))) {
+            if (active && (!lab || label_ok(lab[at], allowed, n_allowed))) {
                 v = tgt[at];
-                fresh = insert(v);
+                fresh = set.insert(v);
             }
-            const unsigned long long fm = __ballot(fresh);
-            if (fm == 0ull) return;
-            uint32_t base = 0;
-            if (lane == 0) base = atomicAdd(&ctl[0], (uint32_t)__builtin_popcountll(fm));
-            base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-            uint32_t pos = base + (uint32_t)__builtin_popcountll(fm & below);
+            WavePlace p = wave_append(fresh, &ctl[0], lane);
+            if (!p.any) return;
             if (!last) {
-                if (fresh && pos < mf) dst[pos] = v;
+                if (fresh && p.pos < mf) dst[p.pos] = v;
                 return;
             }
             bool keep = fresh;
             if (a.mask) {
                 keep = fresh && ((a.mask[v >> 5] >> (v & 31u)) & 1u) != 0u;
-                const unsigned long long km = __ballot(keep);
-                if (km == 0ull) return;
-                if (lane == 0) base = atomicAdd(&ctl[1], (uint32_t)__builtin_popcountll(km));
-                base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-                pos = base + (uint32_t)__builtin_popcountll(km & below);
+                p = wave_append(keep, &ctl[1], lane);
+                if (!p.any) return;
             }
-            if (keep && pos < mf) ids_out[pos] = (unsigned long long)v;
+            if (keep && p.pos < mf) ids_out[p.pos] = (unsigned long long)v;
         };
         for (uint32_t c0 = 0; c0 < n_cur; c0 += 1024u) {
             const bool have = c0 + tid < n_cur;
-            const uint32_t node = have ? cur[c0 + tid] : 0u;
-            for (int pass = 0; pass < 2; ++pass) {
-                const bool use_out = pass == 0;
-                if (use_out && direction == 1u) continue;  // In only
-                if (!use_out && direction == 0u) continue; // Out only
-                const uint64_t *off = use_out ? a.out_off : a.in_off;
-                const uint32_t *tgt = use_out ? a.out_tgt : a.in_tgt;
-                const uint32_t *lab = use_out ? a.out_lab : a.in_lab;
-                const uint64_t a0 = have ? off[node] : 0ull, a1 = have ? off[node + 1] : 0ull;
-                const uint32_t deg = (uint32_t)(a1 - a0); // (the entry points refuse graphs with a row of 2^31 arcs)
-                const bool light = deg <= kLight;
-                uint32_t steps = light ? deg : 0u;
-#pragma unroll
-                for (int sh = 32; sh > 0; sh >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)steps, sh, 64); steps = o > steps ? o : steps; }
-                for (uint32_t i = 0; i < steps && !over(); ++i) take(light && i < deg, tgt, lab, a0 + i);
-                unsigned long long heavy = __ballot(have && !light); // long rows: the whole wavefront strides over the arcs of one node at a time
-                while (heavy && !over()) {
-                    const int l = __builtin_ctzll(heavy);
-                    heavy &= heavy - 1ull;
-                    const uint64_t h0 = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(a0 >> 32), l) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)a0, l);
-                    const uint32_t hdeg = (uint32_t)__builtin_amdgcn_readlane((int)deg, l);
-                    for (uint32_t j = 0; j < hdeg && !over(); j += 64u) take(j + lane < hdeg, tgt, lab, h0 + j + lane);
-                }
-            }
+            walk_rows_per_wave(a.g, direction, have, have ? cur[c0 + tid] : 0u, room, take);
         }
         __syncthreads(); // the hop's set is complete, its list visible to the whole workgroup
         const uint32_t size = ctl[0];
@@ -162,19 +107,6 @@ __global__ __launch_bounds__(1024) void path_lists_kernel(PathListsArgs a) {
 
 namespace hvx {
 
-hipError_t launch_path_lists(const PathListsArgs &args, uint32_t b, hipStream_t s) {
-    if (b == 0) return hipSuccess;
-    PathListsArgs a = args;
-    a.slots = 4096u; // the floor keeps max_frontier + 1 024 below the slot count for small slots
-    while (a.slots < 2u * a.max_frontier) a.slots <<= 1;
-    a.hash_shift = 32u - (uint32_t)__builtin_ctz(a.slots);
-    const size_t lds = (size_t)(kCtlWords + a.slots) * 4u;
-    if (lds > 48 * 1024) { // (a workgroup above 48 KiB asks for it)
-        hipError_t e = hipFuncSetAttribute((const void *)path_lists_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(path_lists_kernel, dim3(b), dim3(1024), lds, s, a);
-    return hipGetLastError();
-}
+hipError_t launch_path_lists(const PathListsArgs &args, uint32_t b, hipStream_t s) { return launch_node_set_kernel(path_lists_kernel, args, b, s); }
 
 } // namespace hvx

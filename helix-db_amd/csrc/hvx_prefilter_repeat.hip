@@ -1,5 +1,5 @@
 // hvx_prefilter_repeat.hip -- repeat(expand).times(n).emit() for a BATCH of requests, every request from its own start nodes
-// (hvx_expand_repeat_lists / hvx_prefilter_repeat_search_lists_params; the entry points live in hvx_prefilter.hip beside the graph handle).
+// (hvx_expand_repeat_lists / hvx_prefilter_repeat_search_lists_params; the entry points live in hvx_prefilter.hip, the graph handle in hvx_csr.h, the row walker and the node set in hvx_csr_dev.h).
 //
 // Reference: g().n(user).repeat(out("follows")).times(3).emit().vector_search(..) runs once per request; the loop is
 // crates/db/src/execution/interpreter/control/repeat.rs:24-99.  On sets, per request:
@@ -26,47 +26,22 @@
 // The kernel is latency-bound (dependent offset -> target -> LDS probe chains), not HBM-bound.
 #include <hip/hip_runtime.h>
 
+#include "hvx_csr_dev.h"
 #include "hvx_host.h"
 
 using namespace hvx;
 
 namespace {
 
-constexpr uint32_t kEmpty = 0xFFFFFFFFu;
-constexpr uint32_t kLight = 16;    // rows up to this long are walked by their own lane
-constexpr uint32_t kCtlWords = 32; // LDS words in front of the table: [0] nodes in the visited set, [1] ids written behind the mask, [2] `until` fired, [8 ..) sizes
-
-__device__ __forceinline__ bool repeat_label_ok(uint32_t lab, const uint32_t *allowed, uint32_t n_allowed) {
-    if (n_allowed == 0) return true; // an empty allow-set means every label (traversal.rs:53)
-    for (uint32_t i = 0; i < n_allowed; ++i)
-        if (allowed[i] == lab) return true;
-    return false;
-}
-
+// LDS control words in front of the table: [0] nodes in the visited set, [1] ids written behind the mask, [2] `until` fired, [8 ..) sizes
 __global__ __launch_bounds__(1024) void repeat_lists_kernel(RepeatListsArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint32_t *ctl = reinterpret_cast<uint32_t *>(smem);
-    uint32_t *tab = ctl + kCtlWords;
+    const LdsNodeSet set{ctl + kNodeSetCtlWords, a.slots, a.hash_shift};
     const uint32_t q = blockIdx.x, tid = threadIdx.x, lane = tid & 63u;
-    const uint32_t mf = a.max_frontier, slot_mask = a.slots - 1u;
-    const unsigned long long below = (1ull << lane) - 1ull;
+    const uint32_t mf = a.max_frontier;
     const bool emit_before = a.emit == (uint32_t)HVX_REPEAT_EMIT_BEFORE, emit_after = a.emit == (uint32_t)HVX_REPEAT_EMIT_AFTER;
-
-    // test-and-set of v in the table; a full table answers "seen" (only a set past max_frontier gets there: its request is over)
-    auto insert = [&](uint32_t v) __attribute__((always_inline)) -> bool {
-        uint32_t h = (v * 0x9E3779B1u) >> a.hash_shift;
-        for (uint32_t probe = 0; probe < a.slots; ++probe) {
-            const uint32_t old = atomicCAS(&tab[h], kEmpty, v);
-            if (old == kEmpty) return true;
-            if (old == v) return false;
-            h = (h + 1u) & slot_mask;
-        }
-        return false;
-    };
-    // wave-uniform: the visited set has outgrown the slot
-    auto over = [&]() __attribute__((always_inline)) -> bool {
-        return (uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(&ctl[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) > mf;
-    };
+    auto room = [&]() __attribute__((always_inline)) -> bool { return !LdsNodeSet::over(&ctl[0], mf); };
 
     unsigned long long *ids_out = a.out_ids + (size_t)q * mf;
     // one emitted node of every lane into the scan's slot, behind the mask.  `pos` = its place when nothing filters and the caller has one
@@ -74,30 +49,24 @@ __global__ __launch_bounds__(1024) void repeat_lists_kernel(RepeatListsArgs a) {
     auto put = [&](bool keep, uint32_t v, uint32_t pos, bool counted) __attribute__((always_inline)) {
         if (a.mask) keep = keep && ((a.mask[v >> 5] >> (v & 31u)) & 1u) != 0u;
         if (a.mask || counted) {
-            const unsigned long long km = __ballot(keep);
-            if (km == 0ull) return;
-            uint32_t base = 0;
-            if (lane == 0) base = atomicAdd(&ctl[1], (uint32_t)__builtin_popcountll(km));
-            base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-            pos = base + (uint32_t)__builtin_popcountll(km & below);
+            const WavePlace p = wave_append(keep, &ctl[1], lane);
+            if (!p.any) return;
+            pos = p.pos;
         }
         if (keep && pos < mf) ids_out[pos] = (unsigned long long)v;
     };
     // one node of every lane: fresh ones take a place in the level under construction (`r0` = the set's size when the level began)
     auto take = [&](bool valid, uint32_t v, uint32_t *dst, uint32_t r0, bool emit_fresh) __attribute__((always_inline)) {
-        const bool fresh = valid && insert(v);
-        const unsigned long long fm = __ballot(fresh);
-        if (fm == 0ull) return;
-        uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(&ctl[0], (uint32_t)__builtin_popcountll(fm));
-        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-        const uint32_t idx = base + (uint32_t)__builtin_popcountll(fm & below);
+        const bool fresh = valid && set.insert(v);
+        const WavePlace p = wave_append(fresh, &ctl[0], lane);
+        if (!p.any) return;
+        const uint32_t idx = p.pos;
         if (fresh && idx < mf) dst[idx - r0] = v; // (idx >= r0: the counter only grows)
         if (emit_fresh) put(fresh, v, idx, false);
     };
 
-    if (tid < kCtlWords) ctl[tid] = 0u;
-    for (uint32_t i = tid; i < a.slots; i += 1024u) tab[i] = kEmpty; // once: the set lives as long as the request
+    if (tid < kNodeSetCtlWords) ctl[tid] = 0u;
+    set.clear(tid); // once: the set lives as long as the request
     __syncthreads();
     const uint32_t s0 = a.seed_off[q];
     uint32_t n_cur = a.seed_off[q + 1] - s0; // (the host has seen it at most max_frontier)
@@ -126,7 +95,7 @@ __global__ __launch_bounds__(1024) void repeat_lists_kernel(RepeatListsArgs a) {
         auto arc = [&](bool active, const uint32_t *tgt, const uint32_t *lab, uint64_t at) __attribute__((always_inline)) {
             uint32_t v = 0;
             bool valid = false;
-            if (active && (!lab || repeat_label_ok(lab[at], a.allowed, a.n_allowed))) {
+            if (active && (!lab || label_ok(lab[at], a.allowed, a.n_allowed))) {
                 v = tgt[at];
                 valid = true;
                 if (a.until) hit = hit || ((a.until[v >> 5] >> (v & 31u)) & 1u) != 0u; // every target, fresh or not
@@ -137,28 +106,14 @@ __global__ __launch_bounds__(1024) void repeat_lists_kernel(RepeatListsArgs a) {
             const bool have = c0 + tid < n_cur;
             const uint32_t node = have ? cur[c0 + tid] : 0u;
             if (emit_before) put(have, node, 0u, true); // the level is emitted as it is expanded
+            // walk_rows_per_wave's loop, kept in the kernel: passed through that helper it costs this kernel 6 more SGPR spills
             for (int pass = 0; pass < 2; ++pass) {
-                const bool use_out = pass == 0;
-                if (use_out && a.direction == 1u) continue;  // In only
-                if (!use_out && a.direction == 0u) continue; // Out only
-                const uint64_t *off = use_out ? a.out_off : a.in_off;
-                const uint32_t *tgt = use_out ? a.out_tgt : a.in_tgt;
-                const uint32_t *lab = use_out ? a.out_lab : a.in_lab;
-                const uint64_t a0 = have ? off[node] : 0ull, a1 = have ? off[node + 1] : 0ull;
-                const uint32_t deg = (uint32_t)(a1 - a0); // (the entry points refuse graphs with a row of 2^31 arcs)
-                const bool light = deg <= kLight;
-                uint32_t steps = light ? deg : 0u;
-#pragma unroll
-                for (int sh = 32; sh > 0; sh >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)steps, sh, 64); steps = o > steps ? o : steps; }
-                for (uint32_t i = 0; i < steps && !over(); ++i) arc(light && i < deg, tgt, lab, a0 + i);
-                unsigned long long heavy = __ballot(have && !light); // long rows: the whole wavefront strides over the arcs of one node at a time
-                while (heavy && !over()) {
-                    const int l = __builtin_ctzll(heavy);
-                    heavy &= heavy - 1ull;
-                    const uint64_t h0 = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(a0 >> 32), l) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)a0, l);
-                    const uint32_t hdeg = (uint32_t)__builtin_amdgcn_readlane((int)deg, l);
-                    for (uint32_t j = 0; j < hdeg && !over(); j += 64u) arc(j + lane < hdeg, tgt, lab, h0 + j + lane);
-                }
+                AdjRow r;
+                if (!adj_pass(a.g, a.direction, pass, have, node, &r)) continue;
+                const bool light = r.deg <= kLightRow;
+                const uint32_t steps = wave_max(light ? r.deg : 0u);
+                for (uint32_t i = 0; i < steps && room(); ++i) arc(light && i < r.deg, r.tgt, r.lab, r.a0 + i);
+                walk_heavy_rows(have && !light, r.a0, r.deg, room, [&](bool active, uint64_t at) __attribute__((always_inline)) { arc(active, r.tgt, r.lab, at); });
             }
         }
         if (hit) ctl[2] = 1u;
@@ -193,19 +148,6 @@ __global__ __launch_bounds__(1024) void repeat_lists_kernel(RepeatListsArgs a) {
 
 namespace hvx {
 
-hipError_t launch_repeat_lists(const RepeatListsArgs &args, uint32_t b, hipStream_t s) {
-    if (b == 0) return hipSuccess;
-    RepeatListsArgs a = args;
-    a.slots = 4096u; // the floor keeps max_frontier + 1 024 below the slot count for small slots
-    while (a.slots < 2u * a.max_frontier) a.slots <<= 1;
-    a.hash_shift = 32u - (uint32_t)__builtin_ctz(a.slots);
-    const size_t lds = (size_t)(kCtlWords + a.slots) * 4u;
-    if (lds > 48 * 1024) { // (a workgroup above 48 KiB asks for it)
-        hipError_t e = hipFuncSetAttribute((const void *)repeat_lists_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(repeat_lists_kernel, dim3(b), dim3(1024), lds, s, a);
-    return hipGetLastError();
-}
+hipError_t launch_repeat_lists(const RepeatListsArgs &args, uint32_t b, hipStream_t s) { return launch_node_set_kernel(repeat_lists_kernel, args, b, s); }
 
 } // namespace hvx
