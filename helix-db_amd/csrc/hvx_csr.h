@@ -61,6 +61,16 @@ struct hvx_csr {
     // control words are [b] lengths | [b] statuses | [b][16] emitted sizes | [b] stop depths -- and adds the `until` predicate's bitmap:
     uint32_t *until_dev = nullptr;                  // [words]
     uint32_t *h_until = nullptr;                    // pinned staging of it
+    // live edits (hvx_csr_apply_edges, hvx_csr_edit.hip), allocated on the first edit: the spare set of the offset and edge-sized
+    // arrays a batch is written into (the two sets swap when the batch is accepted), the plan's staging, the counters
+    uint64_t cap_arcs = 0, cap_arcs2 = 0;           // arcs the live / the spare edge-sized arrays hold
+    uint64_t cap_pc = 0;                            // arcs pc_out / pc_in hold
+    uint64_t *out_off2 = nullptr, *in_off2 = nullptr;
+    uint32_t *out_tgt2 = nullptr, *in_tgt2 = nullptr, *out_lab2 = nullptr, *in_lab2 = nullptr, *in_arc2 = nullptr;
+    void *edit_plan = nullptr;                      // the plan on the device
+    void *h_edit = nullptr;                         // pinned: [64 B read-back of the counters][the plan]
+    size_t cap_edit_plan = 0, cap_h_edit = 0;
+    uint32_t *edit_ctr = nullptr;                   // [4] removals without a stored arc, largest new outgoing row, largest new incoming row
 };
 
 namespace hvx {
@@ -117,5 +127,8 @@ static inline int stage_bitmap(hvx_csr *g, hipStream_t s, const uint64_t *words,
 __attribute__((visibility("hidden"))) int run_bfs_locked(hvx_csr *g, const uint64_t *seeds, uint32_t n_seeds, uint32_t max_depth, uint32_t direction, const uint32_t *labels,
                    uint32_t n_labels, uint32_t hub_degree, uint32_t include_seeds, bool expand_only, uint64_t *out_bitmap, uint32_t *out_depth,
                    hipStream_t consumer = nullptr);
+
+// caller holds g->mu: the host mirror behind hvx_traverse_dfs is dropped (an edit changed the arrays); the next call fetches it again
+__attribute__((visibility("hidden"))) void csr_drop_host_mirror(hvx_csr *g);
 
 } // namespace hvx

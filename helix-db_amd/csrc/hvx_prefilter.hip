@@ -748,10 +748,12 @@ extern "C" int hvx_prefilter_path_search_batch_params(const hvx_index *cix, cons
     hipStream_t s = ix->stream;
     const uint64_t bound = path_bound(g, n_seeds, p);
     const bool lean = lean_route(ix, rp, b, bound); // prefilter_search_impl's rule, over the chain's bound
-    if ((rc = path_stage(g, s, seeds, n_seeds, p, node_mask_words))) return rc;
+    // (a refusal below leaves nothing of this call on the stream: hvx_csr_apply_edges relies on every reader having drained when it gives up g->mu)
+    auto drained = [&](int code) { (void)hipStreamSynchronize(s); return code; };
+    if ((rc = path_stage(g, s, seeds, n_seeds, p, node_mask_words))) return drained(rc);
     if (lean) { // every hop, the row list and the scan behind one host wait
         const uint32_t rows_cap = (uint32_t)std::min<uint64_t>(bound, ix->dev.n);
-        if ((rc = lean_reserve(ix, rows_cap, s))) return rc;
+        if ((rc = lean_reserve(ix, rows_cap, s))) return drained(rc);
         PathHopArgs c;
         memset(&c, 0, sizeof(c));
         c.mask = node_mask_words ? g->mask_dev : nullptr;
@@ -762,11 +764,11 @@ extern "C" int hvx_prefilter_path_search_batch_params(const hvx_index *cix, cons
         c.rows_out = ix->f_subset;
         c.rows_cap = rows_cap;
         c.counters = ix->pf_blocks;
-        if ((rc = path_enqueue(g, s, n_seeds, p, &c))) return rc;
+        if ((rc = path_enqueue(g, s, n_seeds, p, &c))) return drained(rc);
         rc = restricted_direct_shared_devcount(ix, queries, b, k, ix->f_subset, rows_cap, ix->pf_blocks, out_ids, out_scores, out_counts, out_status,
                                                out_candidates, rstats, stats);
     } else {
-        if ((rc = path_enqueue(g, s, n_seeds, p, nullptr))) return rc;
+        if ((rc = path_enqueue(g, s, n_seeds, p, nullptr))) return drained(rc);
         if (node_mask_words) {
             const uint32_t n_words = ((g->n + 63u) / 64u) * 2u;
             hipLaunchKernelGGL(bitmap_and_kernel, dim3((n_words + 255u) / 256u), dim3(256), 0, s, g->visited, g->mask_dev, n_words);

@@ -95,6 +95,7 @@ void csr_free(hvx_csr *g) {
     if (g->h_mask) (void)hipHostFree(g->h_mask);
     if (g->h_until) (void)hipHostFree(g->h_until);
     if (g->h_hops) (void)hipHostFree(g->h_hops);
+    if (g->h_edit) (void)hipHostFree(g->h_edit);
     if (g->done) (void)hipEventDestroy(g->done);
     if (g->stream) (void)hipStreamDestroy(g->stream);
     delete g;
@@ -149,6 +150,7 @@ extern "C" int hvx_csr_import(uint64_t n_nodes, uint64_t n_edges, const uint64_t
     g->device = dev;
     g->n = (uint32_t)n_nodes;
     g->e = n_edges;
+    g->cap_arcs = n_edges;
     auto bail = [&](int code) { csr_free(g); return code; };
     if (hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess) return bail(fail(HVX_ERR_DEVICE, "stream creation failed"));
     int rc;
@@ -537,6 +539,7 @@ extern "C" int hvx_traverse_ordered(const hvx_csr *cg, const uint64_t *seeds, ui
         if ((rc = csr_alloc(g, (void **)&g->owner, nn * 4))) return rc;
         if ((rc = csr_alloc(g, (void **)&g->pc_out, ee * 4))) return rc;
         if ((rc = csr_alloc(g, (void **)&g->pc_in, ee * 4))) return rc;
+        g->cap_pc = ee;
         if ((rc = csr_alloc(g, (void **)&g->cnt, (nn + 1) * 4))) return rc;
         if ((rc = csr_alloc(g, (void **)&g->ord_node, nn * 4))) return rc;
         if ((rc = csr_alloc(g, (void **)&g->ord_parent, nn * 4))) return rc;
@@ -611,6 +614,15 @@ struct HostCsr {
 };
 
 void host_csr_free(void *p) { delete static_cast<HostCsr *>(p); }
+
+} // namespace
+
+void hvx::csr_drop_host_mirror(hvx_csr *g) {
+    host_csr_free(g->host);
+    g->host = nullptr;
+}
+
+namespace {
 
 struct HostArc { uint32_t nb; uint32_t edge; uint32_t against; };
 

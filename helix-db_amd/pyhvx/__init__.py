@@ -405,6 +405,13 @@ def lib():
     L.hvx_csr_import.restype = C.c_int
     L.hvx_csr_import.argtypes = [C.c_uint64, C.c_uint64, _vp, _vp, _vp, C.c_int32, C.POINTER(_vp)]
     L.hvx_csr_free.argtypes = [_vp]
+    L.hvx_csr_apply_edges.restype = C.c_int
+    L.hvx_csr_apply_edges.argtypes = [_vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp, C.c_uint64]
+    L.hvx_csr_sizes.restype = C.c_int
+    L.hvx_csr_sizes.argtypes = [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                C.POINTER(C.c_uint32)]
+    L.hvx_csr_export.restype = C.c_int
+    L.hvx_csr_export.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
     L.hvx_traverse_filter.restype = C.c_int
     L.hvx_traverse_filter.argtypes = [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]
     L.hvx_traverse_ordered.restype = C.c_int
@@ -1360,6 +1367,7 @@ class Graph:
         tgt = np.ascontiguousarray(out_targets, dtype=np.uint64)
         lab = None if edge_labels is None else np.ascontiguousarray(edge_labels, dtype=np.uint32)
         self.n = int(n_nodes)
+        self._labelled = lab is not None
         h = _vp()
         _check(lib().hvx_csr_import(self.n, tgt.size, _ptr(off), _ptr(tgt), _ptr(lab), device, C.byref(h)))
         self._h = h
@@ -1374,6 +1382,46 @@ class Graph:
             self.close()
         except Exception:
             pass
+
+    @staticmethod
+    def _edge_batch(batch):
+        """(src, dst[, labels]) or None -> (src u64, dst u64, labels u32 or None, count)"""
+        if batch is None:
+            return None, None, None, 0
+        src = np.ascontiguousarray(batch[0], dtype=np.uint64)
+        dst = np.ascontiguousarray(batch[1], dtype=np.uint64)
+        lab = np.ascontiguousarray(batch[2], dtype=np.uint32) if len(batch) > 2 and batch[2] is not None else None
+        if src.ndim != 1 or dst.shape != src.shape or (lab is not None and lab.shape != src.shape):
+            raise HelixDbError(ERR_INVARIANT, "an edge batch is (src, dst[, labels]) of one length")
+        return src, dst, lab, src.size
+
+    def apply_edges(self, remove=None, add=None):
+        """One batch of edge removals and additions on the device (hvx_csr_apply_edges): `remove` / `add` = (src, dst[, labels]).
+        Removals first (each deletes the last-stored arc equal to it), then the additions; the handle then equals a fresh import
+        of the edited edge list.  All or nothing."""
+        ds, dd, dl, nd = self._edge_batch(remove)
+        as_, ad, al, na = self._edge_batch(add)
+        _check(lib().hvx_csr_apply_edges(self._h, _ptr(ds), _ptr(dd), _ptr(dl), nd, _ptr(as_), _ptr(ad), _ptr(al), na))
+
+    def sizes(self):
+        """dict(n_nodes, n_edges, max_out_degree, max_in_degree, rows_sorted) of the handle as it stands (hvx_csr_sizes)"""
+        n, e, mo, mi = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        rs = C.c_uint32(0)
+        _check(lib().hvx_csr_sizes(self._h, C.byref(n), C.byref(e), C.byref(mo), C.byref(mi), C.byref(rs)))
+        return dict(n_nodes=n.value, n_edges=e.value, max_out_degree=mo.value, max_in_degree=mi.value, rows_sorted=bool(rs.value))
+
+    def export(self):
+        """The handle's seven arrays on the host (hvx_csr_export): out_offsets, out_targets, out_labels, in_offsets, in_sources,
+        in_labels, in_edge_index; the label arrays are None for an unlabelled graph."""
+        e = self.sizes()["n_edges"]
+        labelled = getattr(self, "_labelled", False)
+        out = dict(out_offsets=np.zeros(self.n + 1, np.uint64), out_targets=np.zeros(e, np.uint64),
+                   out_labels=np.zeros(e, np.uint32) if labelled else None, in_offsets=np.zeros(self.n + 1, np.uint64),
+                   in_sources=np.zeros(e, np.uint64), in_labels=np.zeros(e, np.uint32) if labelled else None,
+                   in_edge_index=np.zeros(e, np.uint64))
+        _check(lib().hvx_csr_export(self._h, *[_ptr(out[k]) for k in ("out_offsets", "out_targets", "out_labels", "in_offsets", "in_sources",
+                                                                        "in_labels", "in_edge_index")]))
+        return out
 
     def traverse(self, seeds, max_depth, direction=DIR_BOTH, allowed_labels=(), hub_degree=0, include_seeds=True):
         s = np.ascontiguousarray(seeds, dtype=np.uint64)

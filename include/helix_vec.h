@@ -457,6 +457,36 @@ int hvx_csr_import(uint64_t n_nodes, uint64_t n_edges, const uint64_t *out_offse
                    const uint64_t *out_targets /*[e]*/, const uint32_t *edge_labels /*[e] or NULL*/,
                    int32_t device, hvx_csr **out);
 void hvx_csr_free(hvx_csr *);
+/* A batch of edge removals and additions applied to a live graph on the device (crates/db/src/mutation/adjacency.rs:12-62,
+ * add_adjacency / remove_adjacency).  Let E be the stored arcs in out-array order, each (src, dst, label); an unlabelled graph has no
+ * label component and its removals match on (src, dst).  The call
+ *   1. applies the removals in batch order: each deletes from E the LAST-stored arc equal to its triple (so add-then-remove of one
+ *      triple is LIFO; a removal never matches an addition of the same batch);
+ *   2. appends the additions in batch order;
+ *   3. stably sorts the result E' by (src, dst).
+ * Afterwards the handle is indistinguishable from hvx_csr_import(n_nodes, |E'|, ...E'...): offsets, targets and labels of both
+ * adjacencies, the incoming rows in (source, out-array position) order, the incoming-slot -> stored-edge map, the exact largest
+ * outgoing / incoming row (they choose the route of the fused prefilter calls) and the edge count.  The stored-edge indices that
+ * hvx_traverse_ordered and hvx_traverse_dfs report index E' from then on.  The node count is fixed: a host that expects growth
+ * imports with spare isolated nodes.
+ * All or nothing: a refused call leaves the handle as it was.  HVX_ERR_INVARIANT: a null required pointer, an endpoint >= n_nodes,
+ * labels passed for an unlabelled graph or missing for a labelled one, a removal with no matching stored arc, more removals of one
+ * triple than arcs stored.  HVX_ERR_UNSUPPORTED: a handle whose imported rows do not ascend by target, |E'| >= 2^32, n_del or
+ * n_add >= 2^31.  n_del == n_add == 0: HVX_OK, nothing changes.
+ * Memory: from its first edit on, a handle holds a second set of its offset and edge-sized arrays (a batch is written into the spare
+ * set and the sets swap when it is accepted; the sets grow geometrically, a steady stream of batches allocates nothing): about
+ * twice the footprint of an imported graph.
+ * Edits are exclusive with every other call on the handle; there are no snapshots or generations for graphs. */
+int hvx_csr_apply_edges(hvx_csr *, const uint64_t *del_src, const uint64_t *del_dst, const uint32_t *del_labels, uint64_t n_del,
+                        const uint64_t *add_src, const uint64_t *add_dst, const uint32_t *add_labels, uint64_t n_add);
+/* What the handle holds now; any pointer may be NULL. */
+int hvx_csr_sizes(const hvx_csr *, uint64_t *n_nodes, uint64_t *n_edges, uint64_t *max_out_degree, uint64_t *max_in_degree,
+                  uint32_t *rows_sorted);
+/* The handle's arrays copied to the host: out_offsets / in_offsets [n + 1], the others [e]; in_edge_index[s] = position in the
+ * outgoing arrays of the stored edge behind incoming slot s.  Any pointer may be NULL; labels of an unlabelled graph =>
+ * HVX_ERR_INVARIANT. */
+int hvx_csr_export(const hvx_csr *, uint64_t *out_offsets, uint64_t *out_targets, uint32_t *out_labels, uint64_t *in_offsets,
+                   uint64_t *in_sources, uint32_t *in_labels, uint64_t *in_edge_index);
 /* Graph::traverse, BreadthFirst (traversal.rs:216-261): multi-seed BFS with depth cap, direction,
  * edge-label allow-set (n_labels==0 => every label) and hub policy (hub_degree>0 => non-seed nodes
  * whose total degree >= hub_degree are emitted but not expanded, :311-318).  Writes a bitmap (1 bit
