@@ -919,3 +919,182 @@ def walk_hop_graph(n_nodes: int, seed: int, sources: int = 1500):
     tgt = np.concatenate([edge_ids, rng.choice(pool, sources - edge_ids.size)]).astype(np.uint64)
     off = np.minimum(np.arange(n_nodes + 1), sources).astype(np.uint64)
     return off, tgt, np.arange(sources, dtype=np.uint64)
+
+
+# ---- the exact scan along the result count and its attempt ladder (test_scan_ladder_fixtures.py proves on the CPU that every corpus
+# ---- below is what tests/test_gpu_scan_result_counts.py says it is)
+# The matrix-core scan tries three certificates in turn (hvx_flat_mfma.hip, flat_mfma_impl): the one-pass contraction with
+# m = max(63, 2 k), the full hi + lo split with the same m, the full split with m = 1023; then the last resort (bf16 rows: the exact tail
+# in sub-batches of 128 queries, f32 rows: the VALU scan, fp8 rows: an error).  Gaussian rows certify at the first one.
+LADDER_M_WIDE = 1023
+SCAN_COUNTS = [10, 511, 1, 128, 31, 257, 64, 32, 127, 65, 256, 255]   # grows and shrinks kc = max(63, 2 k) + 1 across every switch on k
+SCAN_BATCHES = [1, 33, 130]
+SCAN_SHAPES = {"bf16": (5000, 128), "fp8": (5000, 128), "f32": (17500, 256)}   # f32: past 2^22 row elements (the small-batch stream)
+TIE_BLOCKS = [48, 100, 200, 300]
+TIE_CASES_K_T = [(10, 48), (32, 48), (64, 100), (128, 200), (255, 300)]
+_SCAN_IMAGES = {}
+
+
+def stored_rows(rows: str, data: np.ndarray) -> np.ndarray:
+    """the values an index of this row type holds for `data`"""
+    return {"bf16": round_bf16, "fp8": quantize_fp8_rows, "f32": lambda x: np.ascontiguousarray(x, np.float32)}[rows](data)
+
+
+def certificate_holds(approx: np.ndarray, exact: np.ndarray, k: int, m: int, e: float) -> bool:
+    """rerank_bf16_kernel's certificate on modelled scores: the candidates are the m + 1 rows of smallest (approximate score, row), kth
+    is the k-th smallest exact score among them and t the (m + 1)-th approximate score; the answer is certified iff kth < t - e (a
+    scan of at most m rows re-scores every row and needs no certificate)"""
+    if approx.shape[0] <= m:
+        return True
+    order = np.lexsort((np.arange(approx.shape[0]), approx))
+    return bool(np.sort(exact[order[: m + 1]])[k - 1] < approx[order[m]] - e)
+
+
+def scan_image(rows: str):
+    """The image of the result-count tests, built once per process (nobody changes the arrays): a seeded normal corpus of
+    SCAN_SHAPES[rows] (fp8: per-row magnitudes in [0.2, 3]) in which two rows are exact copies of two others and, for every T of
+    TIE_BLOCKS, T rows at scattered positions are copies of one row.  `pool` holds 129 queries: a stored row, a row near each pair of
+    duplicates, a row near each block, and normal draws.  Returns a dict: data (what the index is given), stored (what it holds), dups
+    [(row, its copy)], blocks {T: ascending positions}, near {T: 33 queries next to block T}, pool."""
+    if rows not in _SCAN_IMAGES:
+        n, dim = SCAN_SHAPES[rows]
+        rng = np.random.default_rng({"bf16": 501, "fp8": 502, "f32": 503}[rows])
+        data = rng.standard_normal((n, dim)).astype(np.float32)
+        if rows == "fp8":
+            data *= rng.uniform(0.2, 3.0, (n, 1)).astype(np.float32)
+        if rows == "bf16":
+            data = round_bf16(data)
+        pos = rng.permutation(n)
+        blocks, at = {}, 4
+        for t in TIE_BLOCKS:
+            blocks[t] = np.sort(pos[at:at + t])
+            data[blocks[t]] = data[blocks[t][0]]
+            at += t
+        dups = [(int(pos[0]), int(pos[1])), (int(pos[2]), int(pos[3]))]
+        for a, b in dups:
+            data[b] = data[a]
+        stored = stored_rows(rows, data)
+        # (5 % of the row's own magnitude: fp8 rows differ in theirs)
+        noise = lambda src, cnt: (stored[src][None, :] + 0.05 * np.abs(stored[src]).mean() * rng.standard_normal((cnt, dim))).astype(np.float32)
+        near = {t: noise(blocks[t][0], 33) for t in TIE_BLOCKS}
+        pool = rng.standard_normal((129, dim)).astype(np.float32)
+        pool[0] = stored[int(pos[at])]
+        pool[1], pool[2] = noise(dups[0][0], 1)[0], noise(dups[1][0], 1)[0]
+        for j, t in enumerate(TIE_BLOCKS):
+            pool[3 + j] = near[t][0]
+            pool[40 + j] = near[t][1]      # ... and past the first 32 queries
+        _SCAN_IMAGES[rows] = dict(data=data, stored=stored, dups=dups, blocks=blocks, near=near, pool=pool)
+    return _SCAN_IMAGES[rows]
+
+
+def rung1_fixture(dim: int = 128, k: int = 10, n: int = 3000, ring: int = 80, seed: int = 11):
+    """Rung 1 of the ladder: the one-pass certificate fails and the full split certifies.  Every value -- the hard query's components
+    too -- is a multiple of 2^-5 below 4: exact in bf16, and every squared distance, norm and dot product an exact f32 sum whatever its
+    order.  So the one-pass scores carry NO rounding error, and what fails the first certificate is its bound alone: k rows at distance^2
+    1/4 (one component moved by 1/2), `ring` >= m + 1 rows a gap c^2 further (a second component moved by c), with c^2 the grid's
+    nearest to g = sqrt(E_one E_full) scale -- a factor ~8 inside either bound -- and the rest of the rows two hundred times as far.
+    Returns a dict: data, hard (the query), near / ring (positions), gap (c^2), g, easy (130 queries, a far row + 5 % noise each)."""
+    rng = np.random.default_rng(seed)
+    grid = 2.0 ** -5
+    q = (rng.integers(-48, 49, dim) * grid).astype(np.float32)
+    data = (rng.integers(-64, 65, (n, dim)) * grid).astype(np.float32)
+    scale = error_scale(1, data, q)
+    g = math.sqrt(scan_error_bound(ERR_BF16_ONE_PASS, True, dim) * scan_error_bound(ERR_BF16_FULL, True, dim)) * scale
+    c = max(1.0, float(np.rint(math.sqrt(g) / grid))) * grid
+    pos = rng.permutation(n)
+    near, rpos = np.sort(pos[:k]), np.sort(pos[k:k + ring])
+    for t, p in enumerate(near):
+        data[p] = q
+        data[p, t] += 0.5 if q[t] <= 0 else -0.5
+    for t, p in enumerate(rpos):
+        i = t % dim
+        j = (i + 1 + t // dim) % dim
+        data[p] = q
+        data[p, i] += 0.5 if q[i] <= 0 else -0.5
+        data[p, j] += c if q[j] <= 0 else -c
+    assert error_scale(1, data, q) == scale  # the near rows' norms stay below the corpus's largest
+    src = pos[k + ring:k + ring + 130]
+    easy = (data[src] + 0.05 * rng.standard_normal((130, dim))).astype(np.float32)
+    return dict(data=data, hard=q, near=near, ring=rpos, gap=c * c, g=g, easy=easy)
+
+
+def block_fixture(rows: str, block: int, n: int, dim: int, seed: int, hard: int = 24, easy: int = 130):
+    """Rungs 2 and 3: `block` stored-identical rows at scattered positions are the nearest to every hard query (the row + 5 % noise),
+    the other rows (normal draws) at least ten times as far.  A certificate needs a candidate list that reaches past the block: m = 63
+    never does, m = 1023 does for 500 rows and does not for 1 500.  The block's row is 1.5 times as long as the others, so the plateau of
+    equal scores is nowhere near the top of any other query.  The easy queries are an ordinary row + 5 % noise each, kept only if the
+    modelled one-pass certificate for k = 10 holds with twice its bound: they certify at the first attempt whatever the handle did before.
+    Returns a dict: data, stored, block (ascending positions), hard [hard, dim], easy [easy, dim]."""
+    rng = np.random.default_rng(seed)
+    data = rng.standard_normal((n, dim)).astype(np.float32)
+    pos = rng.permutation(n)
+    bp = np.sort(pos[:block])
+    data[bp] = 1.5 * data[bp[0]]
+    if rows == "bf16":
+        data = round_bf16(data)
+    stored = stored_rows(rows, data)
+    hq = (stored[bp[0]][None, :] + 0.05 * rng.standard_normal((hard, dim))).astype(np.float32)
+    kind = {"bf16": ERR_BF16_ONE_PASS, "fp8": ERR_FP8_ONE_PASS, "f32": ERR_F32_REG_ONE_PASS}[rows]
+    cand = (stored[pos[block:block + 2 * easy]] + 0.05 * rng.standard_normal((2 * easy, dim))).astype(np.float32)
+    ex, ap, _ = l2_model_scores(stored, cand, rows)
+    e = 2.0 * scan_error_bound(kind, True, dim) * l2_error_scales(stored, cand)
+    keep = [i for i in range(cand.shape[0]) if certificate_holds(ap[i], ex[i], 10, 63, e[i])][:easy]
+    assert len(keep) == easy
+    return dict(data=data, stored=stored, block=bp, hard=hq, easy=cand[keep])
+
+
+def l2_model_scores(stored: np.ndarray, qs: np.ndarray, rows: str):
+    """exact_scores and one_pass_scores (one pass, full split) of squared Euclidean for MANY queries at once, [queries, rows] each in
+    f64: the same model with matrix products for the dot products and |x|^2 + |q|^2 - 2 x.q for the exact score (an f64 rounding of
+    ~1e-13 of the norms, far below every bound it is compared with).  Returns (exact, one pass, full split)."""
+    x = _f32(stored).astype(np.float64)
+    qf = _f32(qs)
+    qd = qf.astype(np.float64)
+    qh = round_bf16(qf).astype(np.float64)
+    ql = round_bf16(_f32(qf - round_bf16(qf))).astype(np.float64)
+    if rows == "f32":
+        xh = round_bf16(_f32(stored)).astype(np.float64)
+        xl = round_bf16(_f32(_f32(stored) - round_bf16(_f32(stored)))).astype(np.float64)
+        dot1 = qh @ xh.T
+        dot2 = dot1 + ql @ xh.T + qh @ xl.T
+    else:
+        dot1 = qh @ x.T
+        dot2 = (qh + ql) @ x.T
+    qn2 = (qd ** 2).sum(axis=1)
+    xn2 = (x ** 2).sum(axis=1)
+    qn2f = qn2.astype(np.float32).astype(np.float64)[:, None]
+    xn2f = xn2.astype(np.float32).astype(np.float64)[None, :]
+    exact = np.maximum(qn2[:, None] + xn2[None, :] - 2.0 * (qd @ x.T), 0.0)
+    return exact, np.maximum(qn2f + xn2f - 2.0 * dot1, 0.0), np.maximum(qn2f + xn2f - 2.0 * dot2, 0.0)
+
+
+def l2_error_scales(stored: np.ndarray, qs: np.ndarray) -> np.ndarray:
+    """error_scale of squared Euclidean for every query: (|q|^2 + max |x|^2) / 2"""
+    return 0.5 * ((_f32(qs).astype(np.float64) ** 2).sum(axis=1) + float((_f32(stored).astype(np.float64) ** 2).sum(axis=1).max()))
+
+
+OVERFLOW_FIRST_CHUNK, OVERFLOW_PAIR_CAP = 1024, 1024
+
+
+def overflow_fixture(dim: int = 128, near: int = 4000, b: int = 130, seed: int = 17):
+    """The filtered epilogue's pair buffer: rows 0 .. 1 023 (the first chunk under OPT_FLAT_FIRST_CHUNK = 1024) lie beyond ten times the
+    squared distance of the `near` rows behind them, so the thresholds they give let the whole first filtered slice (3 072 rows) through:
+    more than the 1 024 pairs a query's buffer holds.  bf16 values.  Returns (rows, queries)."""
+    rng = np.random.default_rng(seed)
+    data = rng.standard_normal((OVERFLOW_FIRST_CHUNK + near, dim)).astype(np.float32)
+    data[:OVERFLOW_FIRST_CHUNK] += (8.0 * (rng.integers(0, 2, (OVERFLOW_FIRST_CHUNK, dim)) * 2 - 1)).astype(np.float32)
+    q = rng.standard_normal((b, dim)).astype(np.float32)
+    return round_bf16(data), q
+
+
+_LADDER_BLOCKS = {}
+
+
+def ladder_block(rung: int, rows: str):
+    """block_fixture of rung 2 (500 identical rows of 3 000, dim 128) or rung 3 (1 500 of 4 000; f32 rows: of 17 500 at dim 256, the
+    smallest f32 image a small batch scans on the matrix cores), once per process: nobody changes the arrays"""
+    if (rung, rows) not in _LADDER_BLOCKS:
+        block, n = (500, 3000) if rung == 2 else (1500, 4000)
+        n, dim = (17500, 256) if rows == "f32" else (n, 128)
+        _LADDER_BLOCKS[(rung, rows)] = block_fixture(rows, block, n, dim, seed=100 * rung + ["bf16", "fp8", "f32"].index(rows))
+    return _LADDER_BLOCKS[(rung, rows)]
