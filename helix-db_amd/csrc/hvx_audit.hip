@@ -7,7 +7,11 @@
 //
 //   rows      one thread per stored id: range, ascending order inside the row (=> no duplicates), not the owner, the holes are
 //             trailing sentinels only, degree <= Mmax; one binary search in the target's row for the reverse edge
-//   reach     level-synchronous BFS over layer 0 from the entry point: dist[] claimed with atomicCAS, one launch per level
+//             (exact when the target row is canonical; an id >= n or of a deleted row is out of range and counted in nothing further;
+//             rows of deleted owners are walked like any other -- include/helix_vec.h lists every such decision)
+//   reach     level-synchronous BFS over layer 0 from the entry point: dist[] claimed with atomicCAS, one launch per level; it walks
+//             through deleted rows, which are never counted unreachable
+// Held to a host restatement of these definitions on planted defects of every kind: tests/audit_twin.py, tests/test_gpu_audit.py.
 #include <hip/hip_runtime.h>
 
 #include <cstring>

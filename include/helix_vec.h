@@ -947,6 +947,19 @@ int hvx_index_link_rows(hvx_index *, const uint64_t *from_ids, const uint64_t *t
  * self-free, degree-bounded; mutation.rs:1498-1583,1890-1908: links are bidirectional on their layer) and reachability of every
  * node from the entry point on layer 0.  A graph the reference could have written has every counter below `bfs_levels_l0` at 0
  * (unreachable_l0 may be > 0 for a reference-built graph too: HNSW does not guarantee connectivity).
+ * What is counted, slot by slot (tests/audit_twin.py restates it on the host; tests/test_gpu_audit.py holds the device to it):
+ *   - every slot that is not padding is an edge, whatever else is wrong with it; the rows of deleted nodes are walked like any other
+ *     (a delete empties them) and count for max_degree_*; `nodes` are the live rows, `up_rows` the sum of the levels of all rows;
+ *   - an id >= rows, or the id of a deleted row, is out of range and is counted in nothing further (not asymmetric, no level check);
+ *     an upper-layer id whose node lives below the layer is a level violation and is not also asymmetric; a self loop IS looked up
+ *     for its reverse edge like any other id (it finds itself);
+ *   - the reverse edge is looked up with a binary search over the whole target row, so the asymmetric counts are exact when the
+ *     target rows are canonical (unsorted_entries == 0 and holes == 0); in a row that is not, an id the row holds can be missed;
+ *   - a degree limit of 0 in the descriptor means the row stride (no row overflows);
+ *   - the BFS follows every id < rows, through deleted rows too, but a deleted row is never counted unreachable; bfs_levels_l0 is the
+ *     eccentricity of the entry point; without an entry point every live row is unreachable.
+ * An image after deletes can hold asymmetric edges that are no defect: the reference's relink prunes a row without touching the
+ * rows of what it drops.
  */
 typedef struct hvx_graph_audit {
     uint64_t nodes, up_rows, edges_l0, edges_up;
