@@ -61,6 +61,11 @@ struct hvx_csr {
     // control words are [b] lengths | [b] statuses | [b][16] emitted sizes | [b] stop depths -- and adds the `until` predicate's bitmap:
     uint32_t *until_dev = nullptr;                  // [words]
     uint32_t *h_until = nullptr;                    // pinned staging of it
+    // shortest paths for a batch of requests (hvx_shortest_path_batch, hvx_shortest_path.hip), allocated on first use, grown on demand:
+    // [b][max_depth + 1] u64 paths | [b] lengths | [b] statuses | [b][max_depth] reach sizes | [b][max_reach] u32 discovery order |
+    // [b][slots] u8 levels.  The endpoints travel in h_seeds.
+    void *sp_buf = nullptr;
+    size_t sp_cap = 0;
     // live edits (hvx_csr_apply_edges, hvx_csr_edit.hip), allocated on the first edit: the spare set of the offset and edge-sized
     // arrays a batch is written into (the two sets swap when the batch is accepted), the plan's staging, the counters
     uint64_t cap_arcs = 0, cap_arcs2 = 0;           // arcs the live / the spare edge-sized arrays hold

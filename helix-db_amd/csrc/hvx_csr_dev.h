@@ -86,7 +86,7 @@ __device__ __forceinline__ void walk_rows_per_wave(const CsrView &g, uint32_t di
     }
 }
 
-// The per-workgroup open-addressing set of u32 node numbers in dynamic LDS (path_lists_kernel, repeat_lists_kernel).  kNodeSetCtlWords
+// The per-workgroup open-addressing set of u32 node numbers in dynamic LDS (path_lists_kernel, repeat_lists_kernel, shortest_path_kernel).  kNodeSetCtlWords
 // control words sit in front of the table; word [0] counts the nodes in the set.
 constexpr uint32_t kNodeSetCtlWords = 32;
 struct LdsNodeSet {
@@ -106,6 +106,29 @@ struct LdsNodeSet {
             h = (h + 1u) & (slots - 1u);
         }
         return false;
+    }
+    // insert that also says where: the slot that holds v, *fresh = this call put it there; `slots` (and not fresh) for a full table
+    __device__ __forceinline__ uint32_t insert_slot(uint32_t v, bool *fresh) const {
+        uint32_t h = (v * 0x9E3779B1u) >> shift;
+        *fresh = false;
+        for (uint32_t probe = 0; probe < slots; ++probe) {
+            const uint32_t old = atomicCAS(&tab[h], kEmpty, v);
+            if (old == kEmpty) { *fresh = true; return h; }
+            if (old == v) return h;
+            h = (h + 1u) & (slots - 1u);
+        }
+        return slots;
+    }
+    // read-only probe, for a phase in which nothing inserts: the slot that holds v, or `slots` when v is not in the set
+    __device__ __forceinline__ uint32_t find(uint32_t v) const {
+        uint32_t h = (v * 0x9E3779B1u) >> shift;
+        for (uint32_t probe = 0; probe < slots; ++probe) {
+            const uint32_t at = tab[h];
+            if (at == v) return h;
+            if (at == kEmpty) break;
+            h = (h + 1u) & (slots - 1u);
+        }
+        return slots;
     }
     // wave-uniform: the set, counted in *size, has outgrown `max`.  A wavefront asks before EVERY step, so at most 16 x 64 insertions
     // are in flight when the size crosses `max` and the table cannot fill.

@@ -350,6 +350,20 @@ struct RepeatListsArgs {
     uint32_t *lens, *status, *emit_sizes, *stop_depth; // [b] ids in the slot, [b] HVX_OK / HVX_ERR_CANDIDATE_LIMIT, [b][16] |emitted|, [b]
 };
 hipError_t launch_repeat_lists(const RepeatListsArgs &args, uint32_t b, hipStream_t s);
+// The batched shortest-path kernel (hvx_shortest_path.hip): one workgroup per (source, target) request.
+struct ShortestPathArgs {
+    CsrView g;                                        // the CSR, both adjacencies
+    const uint32_t *src, *dst;                        // pinned host memory, [b] each; 0xFFFFFFFF = the endpoint resolved to no node
+    uint32_t max_depth, direction, n_allowed;         // the plan the batch shares: 1 .. 255 levels, HVX_DIR_*, the label allow-set
+    const uint32_t *allowed;                          // (n_allowed == 0: every label)
+    uint32_t max_frontier;                            // nodes the reach set may hold (the call's max_reach), at most 16 384
+    uint32_t slots, hash_shift;                       // (filled in by launch_node_set_kernel)
+    uint32_t *order;                                  // [b][max_frontier] the reach set in discovery order: level k is a slice of it
+    uint8_t *level;                                   // [b][node_set_slots(max_frontier)] per table slot: the level of the node it holds
+    unsigned long long *out_paths;                    // [b][max_depth + 1] source first
+    uint32_t *lens, *status, *level_sizes;            // [b] nodes of the path, [b] HVX_OK / HVX_ERR_CANDIDATE_LIMIT, [b][max_depth] |reach|
+};
+hipError_t launch_shortest_path(const ShortestPathArgs &args, uint32_t b, hipStream_t s);
 hipError_t launch_stage_ids(const uint64_t *src, const uint32_t *lens, uint32_t stride, uint64_t *dst, uint32_t b, hipStream_t s);
 // exact tail of the small-batch matrix-core scan (hvx_flat_tail.hip): k <= 64, AVX+FMA tree, L2 / cosine, f32 or bf16 rows
 bool flat_tail_supported(const hvx_index *ix, uint32_t b, uint32_t k, uint32_t n_rows);

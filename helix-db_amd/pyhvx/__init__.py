@@ -377,6 +377,11 @@ def lib():
     L.hvx_prefilter_repeat_search_lists_params.argtypes = [_vp, _vp, _vp, C.c_uint32, C.POINTER(RestrictedParams), _vp, _vp, C.c_uint32, C.c_uint32,
                                                            C.c_uint32, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                                            C.POINTER(Stats)]
+    L.hvx_shortest_path_batch.restype = C.c_int
+    L.hvx_shortest_path_batch.argtypes = [_vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]
+    L.hvx_shortest_path_host.restype = C.c_int
+    L.hvx_shortest_path_host.argtypes = [C.c_uint64, C.c_uint64, _vp, _vp, _vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_uint32,
+                                         _vp, C.POINTER(C.c_uint32)]
     L.hvx_batcher_new.restype = C.c_int
     L.hvx_batcher_new.argtypes = [_vp, C.POINTER(_Params), C.c_uint32, C.c_uint32, C.POINTER(_vp)]
     L.hvx_batcher_free.argtypes = [_vp]
@@ -1515,6 +1520,42 @@ class Graph:
                                              _ptr(sizes_flat)))
         sizes = sizes_flat[: b * int(times)].reshape(b, int(times))
         return [ids[q, : lens[q]].copy() for q in range(b)], st[:b], stop[:b], sizes
+
+    def shortest_paths(self, sources, targets, max_depth, direction=DIR_OUT, allowed_labels=(), max_reach=16384):
+        """shortest_path for a batch of (source, target) requests that share max_depth, direction and the label allow-set
+        (hvx_shortest_path_batch): the reference's path, the lexicographically smallest of the shortest ones.  An endpoint that
+        resolved to no node is NO_NODE.  Returns ([path of request q, source first; empty = none within max_depth], statuses,
+        [b][max_depth] sizes of the backward reach set).  A request whose reach set outgrew max_reach (<= 16 384) has status
+        ERR_CANDIDATE_LIMIT and an empty path."""
+        src = np.ascontiguousarray(sources, dtype=np.uint64).reshape(-1)
+        dst = np.ascontiguousarray(targets, dtype=np.uint64).reshape(-1)
+        if src.size != dst.size:
+            raise HelixDbError(ERR_INVARIANT, "sources and targets are of one length")
+        b, md = src.size, int(max_depth)
+        lab = np.ascontiguousarray(list(allowed_labels), dtype=np.uint32)
+        paths = np.zeros((max(b, 1), max(md, 0) + 1), np.uint64)
+        lens = np.zeros(max(b, 1), np.uint32); st = np.zeros(max(b, 1), np.uint32)
+        sizes_flat = np.zeros(max(b, 1) * max(md, 1), np.uint64)
+        _check(lib().hvx_shortest_path_batch(self._h, b, _ptr(src) if b else None, _ptr(dst) if b else None, md, int(direction), _ptr(lab),
+                                             lab.size, int(max_reach), _ptr(paths), _ptr(lens), _ptr(st), _ptr(sizes_flat)))
+        return [paths[q, : lens[q]].copy() for q in range(b)], st[:b], sizes_flat[: b * md].reshape(b, md)
+
+
+NO_NODE = 0xFFFFFFFFFFFFFFFF  # an endpoint of a shortest-path request that resolved to no node
+
+
+def shortest_path_host(n_nodes, out_offsets, out_targets, edge_labels, source, target, max_depth, direction=DIR_OUT, allowed_labels=()):
+    """shortest_path entirely on the host (hvx_shortest_path_host): the reference's literal loop, no device, no Graph handle.
+    Returns the path as a u64 array, source first; empty when there is none of at most max_depth arcs."""
+    off = np.ascontiguousarray(out_offsets, dtype=np.uint64)
+    tgt = np.ascontiguousarray(out_targets, dtype=np.uint64)
+    lab = None if edge_labels is None else np.ascontiguousarray(edge_labels, dtype=np.uint32)
+    al = np.ascontiguousarray(list(allowed_labels), dtype=np.uint32)
+    path = np.zeros(max(int(max_depth), 0) + 1, np.uint64)
+    n = C.c_uint32(0)
+    _check(lib().hvx_shortest_path_host(int(n_nodes), tgt.size, _ptr(off), _ptr(tgt), _ptr(lab), int(source), int(target), int(max_depth),
+                                        int(direction), _ptr(al), al.size, _ptr(path), C.byref(n)))
+    return path[: n.value].copy()
 
 
 def _node_bitmap(words, n, what):

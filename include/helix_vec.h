@@ -657,6 +657,39 @@ int hvx_prefilter_repeat_search_lists_params(const hvx_index *, const hvx_csr *,
                                              uint64_t *out_candidates /*[b] nullable*/, uint32_t *out_stop_depth /*[b] nullable*/,
                                              uint64_t *out_emit_sizes /*[b][times] nullable*/, hvx_stats *stats);
 
+/* shortest_path (execution/interpreter/shortest_path.rs:16-96) for a BATCH of requests that share direction, labels and max_depth and bring
+ * their own (sources[q], targets[q]).  One launch, one workgroup per request.  Per request: source == target answers [source]; otherwise an
+ * unweighted breadth-first search from the source of at most max_depth levels, a node's neighbours being its DISTINCT neighbours in
+ * `direction` whose edge label is allowed (n_labels == 0: every label; the reference's one label is an allow-set of one) in ascending id
+ * order, the first node to discover v in queue order being v's predecessor, the search stopping when the target is discovered.  That path is
+ * the lexicographically smallest (by node id, from the source) of all shortest paths, and that is what the device computes: levels from
+ * the target over the reversed arcs, then from the source always the smallest allowed neighbour one level closer.
+ * out_paths[q * (max_depth + 1) ..) receives the out_lens[q] nodes of the path, source first and target last: 0 = no path of at most
+ * max_depth arcs, 1 = source equals target.  Parallel edges and self-loops are harmless.
+ * Endpoints are resolved by the host (NodeRef, node_exists, the "exactly one node" errors); one that resolved to nothing is passed as
+ * UINT64_MAX: that request answers length 0 with HVX_OK and reach sizes 0.
+ * max_reach (1 .. 16 384) bounds the REACH set: the target and every node the backward search reached.  out_level_sizes[q * max_depth + i] =
+ * its size after level i + 1, or at the loop's end when it ended sooner (the source was reached, a level came up empty; source == target:
+ * 1).  The level in which the source is reached completes.  A request whose reach set outgrows max_reach at level i:
+ * out_status[q] = HVX_ERR_CANDIDATE_LIMIT, out_lens[q] = 0, level i's size reported as max_reach + 1 and later ones as 0 (overflow wins over
+ * a source reached in the same level); the other requests are unaffected and the call returns HVX_OK.  Such a request goes through
+ * hvx_traverse_ordered, one at a time, and its out_parents.
+ * Refused before anything is enqueued: HVX_ERR_INVARIANT for a null required pointer, a bad direction, max_depth == 0, an endpoint
+ * >= n_nodes that is not UINT64_MAX; HVX_ERR_UNSUPPORTED for max_depth > 255, max_reach 0 or above 16 384, more than 65 535 requests.
+ * b == 0: HVX_OK.  Exclusive with hvx_csr_apply_edges on the same handle, like every hvx_expand_* call. */
+int hvx_shortest_path_batch(const hvx_csr *, uint32_t b, const uint64_t *sources /*[b]*/, const uint64_t *targets /*[b]*/,
+                            uint32_t max_depth, uint32_t direction, const uint32_t *allowed_label_ids, uint32_t n_labels,
+                            uint32_t max_reach, uint64_t *out_paths /*[b][max_depth + 1]*/, uint32_t *out_lens /*[b]*/,
+                            uint32_t *out_status /*[b]*/, uint64_t *out_level_sizes /*[b][max_depth] nullable*/);
+/* One request entirely on the host, over caller-held arrays (no device, no hvx_csr): the reference's literal loop -- queue, visited set,
+ * predecessor map, sorted distinct neighbours, stop at discovery.  The incoming adjacency is built once per call.  *out_len as above; an
+ * endpoint passed as UINT64_MAX answers length 0.  HVX_ERR_INVARIANT for a null required pointer, a bad direction, max_depth == 0, an
+ * endpoint or arc target >= n_nodes, offsets that do not ascend to n_edges. */
+int hvx_shortest_path_host(uint64_t n_nodes, uint64_t n_edges, const uint64_t *out_offsets, const uint64_t *out_targets,
+                           const uint32_t *edge_labels /*nullable*/, uint64_t source, uint64_t target, uint32_t max_depth,
+                           uint32_t direction, const uint32_t *allowed_label_ids, uint32_t n_labels,
+                           uint64_t *out_path /*[max_depth + 1]*/, uint32_t *out_len);
+
 /*
  * Batching operator: the reference calls ValidatedVectorReadIndex::search once per operator invocation
  * from many tokio tasks (access/search/storage.rs:140-163).  Concurrent single-query callers are coalesced into ONE
