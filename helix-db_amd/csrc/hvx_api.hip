@@ -799,7 +799,7 @@ int hvx::enqueue_search(const hvx_index *cix, const float *d_queries, uint32_t b
     if (ad) {
         if (!hnsw_wave_adaptive_supported(a))
             return fail(HVX_ERR_UNSUPPORTED, "the non-strict search arms serve f32 rows of any dimension / metric (bf16 rows: dim in "
-                        "{128,256,512,768,1024,1536}, cosine / Euclidean), neighbour rows <= 64 ids, ef <= 800");
+                        "{128,256,384,512,768,1024,1536}, cosine / Euclidean), neighbour rows <= 64 ids, ef <= 800");
         if (ix->bitmap_dirty) {
             HIP_TRY(hipMemsetAsync(ix->d_bitmap, 0, (size_t)ix->max_batch * ix->words_per_query * 4, ix->stream));
             ix->bitmap_dirty = false;
@@ -837,7 +837,7 @@ int hvx::enqueue_search(const hvx_index *cix, const float *d_queries, uint32_t b
     const bool wave = !(force_general && ix->dev.dtype == HVX_F32) && hnsw_wave_supported(a);
     if (!wave && ix->dev.dtype != HVX_F32)
         return fail(HVX_ERR_UNSUPPORTED, ix->dev.dtype == HVX_FP8_E4M3 ? "fp8 rows serve the exact scan only (HNSW over fp8 rows is not built)"
-                    : "bf16 rows are served by the one-wavefront-per-query kernel only (dim in {128,256,512,768,1024,1536}, rows <= 64 ids, ef <= 800)");
+                    : "bf16 rows are served by the one-wavefront-per-query kernel only (dim in {128,256,384,512,768,1024,1536}, rows <= 64 ids, ef <= 800)");
     if (ix->bitmap_dirty) {
         HIP_TRY(hipMemsetAsync(ix->d_bitmap, 0, (size_t)ix->max_batch * ix->words_per_query * 4, ix->stream));
         ix->bitmap_dirty = false;
