@@ -66,6 +66,11 @@ struct hvx_csr {
     // [b][slots] u8 levels.  The endpoints travel in h_seeds.
     void *sp_buf = nullptr;
     size_t sp_cap = 0;
+    // shortest paths of any reach (hvx_shortest_path_batch_dense, hvx_shortest_path_dense.hip), allocated on first use, grown on demand:
+    // the sibling's outputs ([b][max_depth + 1] u64 paths | [b] lengths | [b] statuses | [b][max_depth] reach sizes) | [b] x 5 u32 request
+    // words | [groups] u64 active | [2][groups] u64 grew || one round of hvx_shortest_path_dense_plan.h's node state (88 B per node and group)
+    void *spd_buf = nullptr;
+    size_t spd_cap = 0;
     // live edits (hvx_csr_apply_edges, hvx_csr_edit.hip), allocated on the first edit: the spare set of the offset and edge-sized
     // arrays a batch is written into (the two sets swap when the batch is accepted), the plan's staging, the counters
     uint64_t cap_arcs = 0, cap_arcs2 = 0;           // arcs the live / the spare edge-sized arrays hold
@@ -87,6 +92,22 @@ static inline int csr_alloc(hvx_csr *g, void **p, size_t bytes) {
     hipError_t e = hipMalloc(p, bytes);
     if (e != hipSuccess) return fail(HVX_ERR_DEVICE, "hipMalloc(%zu): %s", bytes, hipGetErrorString(e));
     g->allocs.push_back(*p);
+    return HVX_OK;
+}
+
+// caller holds g->mu.  A grow-on-demand device buffer of the handle (*buf, *cap) of at least `bytes`; every call that used the old one has
+// waited for its stream.
+static inline int csr_reserve(hvx_csr *g, void **buf, size_t *cap, size_t bytes) {
+    if (bytes <= *cap) return HVX_OK;
+    if (*buf) {
+        g->allocs.erase(std::remove(g->allocs.begin(), g->allocs.end(), *buf), g->allocs.end());
+        (void)hipFree(*buf);
+        *buf = nullptr;
+        *cap = 0;
+    }
+    int rc = csr_alloc(g, buf, bytes);
+    if (rc) return rc;
+    *cap = bytes;
     return HVX_OK;
 }
 
@@ -132,6 +153,9 @@ static inline int stage_bitmap(hvx_csr *g, hipStream_t s, const uint64_t *words,
 __attribute__((visibility("hidden"))) int run_bfs_locked(hvx_csr *g, const uint64_t *seeds, uint32_t n_seeds, uint32_t max_depth, uint32_t direction, const uint32_t *labels,
                    uint32_t n_labels, uint32_t hub_degree, uint32_t include_seeds, bool expand_only, uint64_t *out_bitmap, uint32_t *out_depth,
                    hipStream_t consumer = nullptr);
+
+// what both shortest-path batch calls and the host loop refuse about the plan the requests share (hvx_shortest_path.hip)
+__attribute__((visibility("hidden"))) int shortest_path_plan_check(uint32_t max_depth, uint32_t direction, const uint32_t *allowed_label_ids, uint32_t n_labels);
 
 // caller holds g->mu: the host mirror behind hvx_traverse_dfs is dropped (an edit changed the arrays); the next call fetches it again
 __attribute__((visibility("hidden"))) void csr_drop_host_mirror(hvx_csr *g);

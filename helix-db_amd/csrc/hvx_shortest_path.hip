@@ -154,31 +154,16 @@ constexpr uint32_t kMaxReach = 16384; // 32 768 table slots x 4 B = 128 KiB of a
 constexpr uint32_t kMaxBatch = 65535;
 constexpr uint32_t kMaxDepth = 255;   // a level is a byte
 
-int plan_check(uint32_t max_depth, uint32_t direction, const uint32_t *allowed_label_ids, uint32_t n_labels) {
+} // namespace
+
+namespace hvx {
+
+int shortest_path_plan_check(uint32_t max_depth, uint32_t direction, const uint32_t *allowed_label_ids, uint32_t n_labels) {
     if (direction > HVX_DIR_BOTH) return fail(HVX_ERR_INVARIANT, "bad direction %u", direction);
     if (max_depth == 0) return fail(HVX_ERR_INVARIANT, "shortest_path searches at least one level");
     if (n_labels && !allowed_label_ids) return fail(HVX_ERR_INVARIANT, "null labels");
     return HVX_OK;
 }
-
-// g->sp_buf of at least `bytes` (every call that used the old one has waited for its stream)
-int sp_reserve(hvx_csr *g, size_t bytes) {
-    if (bytes <= g->sp_cap) return HVX_OK;
-    if (g->sp_buf) {
-        g->allocs.erase(std::remove(g->allocs.begin(), g->allocs.end(), g->sp_buf), g->allocs.end());
-        (void)hipFree(g->sp_buf);
-        g->sp_buf = nullptr;
-        g->sp_cap = 0;
-    }
-    int rc = csr_alloc(g, &g->sp_buf, bytes);
-    if (rc) return rc;
-    g->sp_cap = bytes;
-    return HVX_OK;
-}
-
-} // namespace
-
-namespace hvx {
 
 hipError_t launch_shortest_path(const ShortestPathArgs &args, uint32_t b, hipStream_t s) { return launch_node_set_kernel(shortest_path_kernel, args, b, s); }
 
@@ -189,7 +174,7 @@ extern "C" int hvx_shortest_path_batch(const hvx_csr *cg, uint32_t b, const uint
                                        uint64_t *out_paths, uint32_t *out_lens, uint32_t *out_status, uint64_t *out_level_sizes) {
     if (!cg || !out_paths || !out_lens || !out_status || (b && (!sources || !targets))) return fail(HVX_ERR_INVARIANT, "null argument");
     hvx_csr *g = const_cast<hvx_csr *>(cg);
-    int rc = plan_check(max_depth, direction, allowed_label_ids, n_labels);
+    int rc = shortest_path_plan_check(max_depth, direction, allowed_label_ids, n_labels);
     if (rc) return rc;
     if (max_depth > kMaxDepth) return fail(HVX_ERR_UNSUPPORTED, "shortest_path on the device searches at most %u levels, not %u", kMaxDepth, max_depth);
     if (max_reach == 0 || max_reach > kMaxReach)
@@ -213,7 +198,7 @@ extern "C" int hvx_shortest_path_batch(const hvx_csr *cg, uint32_t b, const uint
     // [b][max_depth + 1] u64 paths | [b] lengths | [b] statuses | [b][max_depth] sizes || [b][max_reach] u32 order | [b][slots] u8 levels
     const uint32_t slots = node_set_slots(max_reach);
     const size_t path_words = (size_t)b * (max_depth + 1u), ctl_words = (size_t)b * (2u + max_depth), back_bytes = path_words * 8 + ctl_words * 4;
-    if ((rc = sp_reserve(g, back_bytes + (size_t)b * max_reach * 4 + (size_t)b * slots))) return rc;
+    if ((rc = csr_reserve(g, &g->sp_buf, &g->sp_cap, back_bytes + (size_t)b * max_reach * 4 + (size_t)b * slots))) return rc;
     ShortestPathArgs a;
     memset(&a, 0, sizeof(a));
     a.g = csr_view(g);
@@ -251,7 +236,7 @@ extern "C" int hvx_shortest_path_host(uint64_t n_nodes, uint64_t n_edges, const 
                                       const uint32_t *allowed_label_ids, uint32_t n_labels, uint64_t *out_path, uint32_t *out_len) {
     if (!out_offsets || (n_edges && !out_targets) || !out_path || !out_len) return fail(HVX_ERR_INVARIANT, "null argument");
     *out_len = 0;
-    int rc = plan_check(max_depth, direction, allowed_label_ids, n_labels);
+    int rc = shortest_path_plan_check(max_depth, direction, allowed_label_ids, n_labels);
     if (rc) return rc;
     for (const uint64_t v : {source, target})
         if (v >= n_nodes && v != UINT64_MAX) return fail(HVX_ERR_INVARIANT, "unknown node %llu", (unsigned long long)v);

@@ -379,6 +379,8 @@ def lib():
                                                            C.POINTER(Stats)]
     L.hvx_shortest_path_batch.restype = C.c_int
     L.hvx_shortest_path_batch.argtypes = [_vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]
+    L.hvx_shortest_path_batch_dense.restype = C.c_int
+    L.hvx_shortest_path_batch_dense.argtypes = [_vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint32, C.c_uint64, _vp, _vp, _vp, _vp]
     L.hvx_shortest_path_host.restype = C.c_int
     L.hvx_shortest_path_host.argtypes = [C.c_uint64, C.c_uint64, _vp, _vp, _vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_uint32,
                                          _vp, C.POINTER(C.c_uint32)]
@@ -1539,6 +1541,25 @@ class Graph:
         _check(lib().hvx_shortest_path_batch(self._h, b, _ptr(src) if b else None, _ptr(dst) if b else None, md, int(direction), _ptr(lab),
                                              lab.size, int(max_reach), _ptr(paths), _ptr(lens), _ptr(st), _ptr(sizes_flat)))
         return [paths[q, : lens[q]].copy() for q in range(b)], st[:b], sizes_flat[: b * md].reshape(b, md)
+
+    def shortest_paths_dense(self, sources, targets, max_depth, direction=DIR_OUT, allowed_labels=(), scratch_bytes=0, sizes=True):
+        """shortest_paths without a reach limit (hvx_shortest_path_batch_dense): 64 requests share one bit-parallel sweep over the
+        arcs, the per-node state (88 bytes per node and group of 64 requests) lives in device memory within scratch_bytes (0 = 1 GiB)
+        and groups that do not fit together run in rounds.  Returns the same triple as shortest_paths; every status is OK.
+        sizes=False does not ask for the reach sizes (the third element is then None)."""
+        src = np.ascontiguousarray(sources, dtype=np.uint64).reshape(-1)
+        dst = np.ascontiguousarray(targets, dtype=np.uint64).reshape(-1)
+        if src.size != dst.size:
+            raise HelixDbError(ERR_INVARIANT, "sources and targets are of one length")
+        b, md = src.size, int(max_depth)
+        lab = np.ascontiguousarray(list(allowed_labels), dtype=np.uint32)
+        paths = np.zeros((max(b, 1), max(md, 0) + 1), np.uint64)
+        lens = np.zeros(max(b, 1), np.uint32); st = np.zeros(max(b, 1), np.uint32)
+        sizes_flat = np.zeros(max(b, 1) * max(md, 1), np.uint64) if sizes else None
+        _check(lib().hvx_shortest_path_batch_dense(self._h, b, _ptr(src) if b else None, _ptr(dst) if b else None, md, int(direction),
+                                                   _ptr(lab), lab.size, int(scratch_bytes), _ptr(paths), _ptr(lens), _ptr(st),
+                                                   _ptr(sizes_flat)))
+        return ([paths[q, : lens[q]].copy() for q in range(b)], st[:b], sizes_flat[: b * md].reshape(b, md) if sizes else None)
 
 
 NO_NODE = 0xFFFFFFFFFFFFFFFF  # an endpoint of a shortest-path request that resolved to no node
