@@ -635,19 +635,16 @@ __device__ __forceinline__ void hnsw_wave_query(const HnswArgs &a, const uint32_
     constexpr int kFL = (kWide4 ? 4 * P : (kWide2 ? 2 * P : P)) * NL;
     constexpr int kSWmax = !SP ? 1 : 8 * SL * 4 <= kFL * 3 ? 8 : 4 * SL * 4 <= kFL * 3 ? 4 : 3 * SL * 4 <= kFL * 3 ? 3 : 2 * SL * 4 <= kFL * 3 ? 2 : 1;
     const bool shadow_on = SP && a.shadow != nullptr;
-    // one shadow pass of W rows per group over fr_id[f0..nf): per-row lower bound -> fr_d[f]
+    // one shadow pass of W rows per group over fr_id[f0..nf): per-row sum of squared differences against the shadow -> fr_d[f]
     auto shadow_pass = [&](auto width, uint32_t f0, uint32_t nf) __attribute__((always_inline)) {
         constexpr int W = decltype(width)::value;
         uint32_t nd[W];
         uint4 x[W][SL];
-        float e[W];
 #pragma unroll
         for (int p = 0; p < W; ++p) {
             const uint32_t f = f0 + (uint32_t)(p * 8 + grp);
             nd[p] = fr_id[f < nf ? f : f0]; // idle groups shadow the pass's first row
         }
-#pragma unroll
-        for (int p = 0; p < W; ++p) e[p] = a.shadow_err[nd[p]];
 #pragma unroll
         for (int p = 0; p < W; ++p) {
             const uint4 *rp = reinterpret_cast<const uint4 *>(a.shadow + (size_t)nd[p] * ix.dim) + j;
@@ -661,6 +658,18 @@ __device__ __forceinline__ void hnsw_wave_query(const HnswArgs &a, const uint32_
         const float4 *qp = reinterpret_cast<const float4 *>(qs) + 2 * j; // lane j's 16 bytes of load k = elements 8 (8k + j) .. + 7
 #pragma unroll
         for (int k = 0; k < SL; ++k) {
+            // A two-per-SIMD pass whose rows alone take 144 of the wavefront's 256 registers (three rows at dim 768: the headline
+            // build) is at the register budget with one step's query pieces and widened halfwords.  Left free, the scheduler moves
+            // the later steps' reads and widening to the top of the pass and spills 26 registers (it did not while the W bounds
+            // were still evaluated in this pass).  Empty asm statements tie each step's reads (memory clobber) and widening (the
+            // step's row registers) behind the previous step's FMAs: the order of the parent's assembly.  They emit nothing.
+            // scripts/kernel_meta.py on the built library is the guard: run it again whenever the toolchain changes.
+            if (OCC == 2 && W * SL * 4 >= 144 && k > 0) {
+#pragma unroll
+                for (int p = 0; p < W; ++p) asm volatile("" : "+v"(acc[p].x), "+v"(acc[p].y), "+v"(acc[p].z), "+v"(acc[p].w) : : "memory");
+#pragma unroll
+                for (int p = 0; p < W; ++p) asm volatile("" : "+v"(x[p][k].x), "+v"(x[p][k].y), "+v"(x[p][k].z), "+v"(x[p][k].w));
+            }
             const float4 q0 = qp[16 * k], q1 = qp[16 * k + 1];
 #pragma unroll
             for (int p = 0; p < W; ++p) { // bf16 -> f32 is exact: the halfword becomes the high half of the word
@@ -674,16 +683,24 @@ __device__ __forceinline__ void hnsw_wave_query(const HnswArgs &a, const uint32_
 #pragma unroll
         for (int p = 0; p < W; ++p) {
             float r = (acc[p].x + acc[p].y) + (acc[p].z + acc[p].w); // summation order is free for the bound
-            r += __shfl_xor(r, 1, 8);
-            r += __shfl_xor(r, 2, 8);
-            r += __shfl_xor(r, 4, 8);
+            // lane ^ 1, lane ^ 2, then the other quad of the 8-lane group: after two steps a quad's lanes hold one value, so the
+            // half-row mirror (7 - l) delivers what lane ^ 4 would -- the add tree of three LDS permutes, without LDS
+            r += dpp_xor1(r);
+            r += dpp_xor2(r);
+            r += dpp_half_mirror(r);
             const uint32_t f = f0 + (uint32_t)(p * 8 + grp);
-            if (f < nf && j == 0) fr_d[f] = shadow_l2_lower_bound(r, e[p], ix.dim);
+            if (f < nf && j == 0) fr_d[f] = r;
         }
     };
-    // frontier fr_id[0..nf) -> the rows the bound does not reject, compacted in frontier order; returns their number
+    // frontier fr_id[0..nf) -> the rows the bound does not reject, compacted in frontier order; returns their number.
+    // Lane f owns frontier row f: it requests the row's rounding residual ahead of the passes' row loads, evaluates the bound
+    // once from the sum its group left in fr_d[f], and keeps the id it read at the start for the compaction.  (One wavefront:
+    // its LDS operations execute in order, the compacting writes need no fence of their own behind the reads.)
     auto shadow_prune = [&](uint32_t nf, float thr) __attribute__((always_inline)) -> uint32_t {
         if constexpr (SP) {
+            const bool in = (uint32_t)lane < nf;
+            const uint32_t id = in ? fr_id[lane] : kSentinel;
+            const float e = in ? a.shadow_err[id] : 0.f;
             uint32_t f0 = 0;
             while (f0 < nf) {
                 const uint32_t rem = nf - f0;
@@ -694,11 +711,9 @@ __device__ __forceinline__ void hnsw_wave_query(const HnswArgs &a, const uint32_
                 else { shadow_pass(std::integral_constant<int, 1>{}, f0, nf); f0 += 8u; }
             }
             __syncthreads();
-            const bool in = (uint32_t)lane < nf;
-            const uint32_t id = in ? fr_id[lane] : kSentinel;
-            const bool keep = in && !(fr_d[in ? lane : 0] > thr); // strict: a row whose bound equals the threshold is scored
+            const float lb = shadow_l2_lower_bound(fr_d[in ? lane : 0], e, ix.dim);
+            const bool keep = in && !(lb > thr); // strict: a row whose bound equals the threshold is scored
             const unsigned long long km = __ballot(keep);
-            __syncthreads();
             if (keep) fr_id[__builtin_popcountll(km & ((1ull << lane) - 1ull))] = id;
             __syncthreads();
             return (uint32_t)__builtin_popcountll(km);
