@@ -640,7 +640,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         } else {
             Gather<NK, P, BFR> g;
             gather_issue<NK, P, BFR, P, METRIC == kCosine>(ix, nd, slot, g);
-            gather_consume<METRIC, NK, P, BFR>(ix, qs, g, nd, slot, qhdr, qglobal, o);
+            gather_consume<METRIC, NK, P, BFR, P, false>(ix, qs, g, nd, slot, qhdr, qglobal, o); // component-wise: the packed form was measured on the HNSW beam only
         }
 #pragma unroll
         for (int p = 0; p < P; ++p) {

@@ -45,6 +45,7 @@ __global__ __launch_bounds__(64 * (1 + G)) __attribute__((amdgpu_waves_per_eu(1 
     constexpr int NL = BF ? NK / 2 : NK; // 16-byte loads per lane and row
     constexpr int P = NL <= 8 ? 2 : 1;
     constexpr bool kWide2 = G == 1 && 2 * P * NL <= 48 && !(BF && METRIC == kCosine && NL >= 24); // 192 of the gatherer's 256 registers (cosine over bf16 rows at dim 1536 spilled 72: one row per group)
+    constexpr bool PK = true; // packed FMAs in the gatherers (hvx_hnsw_wave.h: fma_chunk): no build of this kernel spills more with them
     constexpr uint32_t kThreads = 64u * (1u + G);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const DevIndex &ix = a.ix;
@@ -91,7 +92,7 @@ __global__ __launch_bounds__(64 * (1 + G)) __attribute__((amdgpu_waves_per_eu(1 
                 nd[p] = fr_id[f < nf ? f : f0]; // idle groups shadow the pass's first row
             }
             gather_issue<NK, W, BF, W, METRIC == kCosine>(ix, nd, slot, g);
-            gather_consume<METRIC, NK, W, BF>(ix, qs, g, nd, slot, qhdr, qglobal, o);
+            gather_consume<METRIC, NK, W, BF, W, PK>(ix, qs, g, nd, slot, qhdr, qglobal, o);
 #pragma unroll
             for (int p = 0; p < W; ++p) {
                 const uint32_t f = f0 + (uint32_t)(p * 8 + grp);

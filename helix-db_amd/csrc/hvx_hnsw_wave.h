@@ -229,46 +229,109 @@ template <uint32_t METRIC> __device__ __forceinline__ void fma_chunk(float4 &acc
     }
 }
 
+// The same step on register pairs: a float4 accumulator as two packed halves, one v_pk_add_f32 + one v_pk_fma_f32 per half
+// (cosine: the fma alone).  Written with vector types, so the packed instructions do not depend on the SLP vectorizer finding
+// them (it packed the one-row f32 pass of the headline build and nothing else).  Component by component these are the float4
+// form's IEEE operations (one subtract, one fused multiply-add, the same chain over k): same bits.  Half the FMA instructions
+// and, in most builds, fewer registers; in cycles 1 to 8 % of the f32 gather phase, and no benchmark gain that clears the
+// run-to-run spread (profiles/packed_fma_prof.log) -- the shadow pass, slower in this form, keeps the other.
+// PK = false keeps the component-wise form for the instantiations that are at their register budget (packed operands need
+// even-aligned register pairs; packed_fma_build below names them).
+typedef float f2 __attribute__((ext_vector_type(2)));
+struct Acc4 { f2 lo, hi; };
+__device__ __forceinline__ f2 bf16_pair_widen(uint32_t w) { // bf16 -> f32 is exact: the halfword becomes the high half of the word
+    return f2{__uint_as_float(w << 16), __uint_as_float(w & 0xFFFF0000u)};
+}
+template <uint32_t METRIC, bool PK>
+__device__ __forceinline__ void fma_chunk(Acc4 &acc, const f2 ql, const f2 qh, const f2 xl, const f2 xh) {
+    if (PK) {
+        if (METRIC == kL2) {
+            const f2 d0 = ql - xl, d1 = qh - xh;
+            acc.lo = __builtin_elementwise_fma(d0, d0, acc.lo);
+            acc.hi = __builtin_elementwise_fma(d1, d1, acc.hi);
+        } else {
+            acc.lo = __builtin_elementwise_fma(ql, xl, acc.lo);
+            acc.hi = __builtin_elementwise_fma(qh, xh, acc.hi);
+        }
+    } else if (METRIC == kL2) {
+        const float d0 = ql.x - xl.x, d1 = ql.y - xl.y, d2 = qh.x - xh.x, d3 = qh.y - xh.y;
+        acc.lo.x = __builtin_fmaf(d0, d0, acc.lo.x); acc.lo.y = __builtin_fmaf(d1, d1, acc.lo.y);
+        acc.hi.x = __builtin_fmaf(d2, d2, acc.hi.x); acc.hi.y = __builtin_fmaf(d3, d3, acc.hi.y);
+    } else {
+        acc.lo.x = __builtin_fmaf(ql.x, xl.x, acc.lo.x); acc.lo.y = __builtin_fmaf(ql.y, xl.y, acc.lo.y);
+        acc.hi.x = __builtin_fmaf(qh.x, xh.x, acc.hi.x); acc.hi.y = __builtin_fmaf(qh.y, xh.y, acc.hi.y);
+    }
+}
+
+// Packing is on unless the instantiation is named here: the 51 builds of hnsw_wave_kernel whose packed form spilled more
+// vector or scalar registers, or used more scratch, than the component-wise one -- scalar spills alone in 50 of them, by 1 to
+// 36 registers, mostly the non-strict arms, which sit at their scalar budget (scripts/kernel_meta.py on both libraries;
+// profiles/packed_fma_kernel_meta.json; DESIGN.md 4.1 lists them with their register counts).  They compile to the parent's
+// code.  Run the comparison again whenever the toolchain changes.  No build of the pair kernel is among them: its gatherers
+// always pack.
+struct PackedOptOut { uint32_t metric; int r, nk; bool bf, ad, st; int occ; bool build; };
+constexpr PackedOptOut kPackedOptOut[] = {
+    {0u, 3, 12, 0, 0, 1, 1, 1}, {0u, 3, 24, 0, 0, 1, 1, 1}, {0u, 6, 16, 0, 0, 1, 2, 0}, {0u, 6, 24, 0, 0, 1, 2, 0},
+    {0u, 6, 32, 0, 0, 1, 1, 0}, {0u, 13, 24, 0, 0, 1, 2, 0}, {1u, 6, 48, 0, 0, 1, 2, 1}, {0u, 3, 8, 0, 1, 0, 2, 0},
+    {0u, 3, 12, 0, 1, 0, 1, 0}, {0u, 3, 16, 0, 1, 1, 1, 0}, {0u, 3, 16, 0, 1, 1, 2, 0}, {0u, 3, 24, 0, 1, 0, 1, 0},
+    {0u, 3, 24, 0, 1, 1, 2, 0}, {0u, 3, 32, 0, 1, 0, 2, 0}, {0u, 3, 48, 0, 1, 1, 1, 0}, {0u, 3, 48, 0, 1, 1, 2, 0},
+    {0u, 6, 12, 0, 1, 0, 1, 0}, {0u, 6, 16, 0, 1, 1, 1, 0}, {0u, 6, 16, 0, 1, 1, 2, 0}, {0u, 6, 24, 0, 1, 0, 1, 0},
+    {0u, 6, 24, 0, 1, 0, 2, 0}, {0u, 6, 48, 0, 1, 0, 1, 0}, {0u, 6, 48, 0, 1, 1, 2, 0}, {1u, 3, 4, 0, 1, 0, 2, 0},
+    {1u, 3, 16, 0, 1, 1, 1, 0}, {1u, 3, 16, 0, 1, 1, 2, 0}, {1u, 3, 48, 0, 1, 1, 2, 0}, {1u, 6, 4, 0, 1, 0, 1, 0},
+    {1u, 6, 8, 0, 1, 0, 2, 0}, {1u, 6, 12, 0, 1, 1, 1, 0}, {1u, 6, 16, 0, 1, 1, 1, 0}, {1u, 6, 24, 0, 1, 1, 1, 0},
+    {1u, 3, 4, 1, 1, 1, 1, 0}, {1u, 3, 8, 1, 1, 0, 1, 0}, {1u, 3, 12, 1, 1, 0, 2, 0}, {1u, 3, 16, 1, 1, 1, 1, 0},
+    {1u, 3, 16, 1, 1, 1, 2, 0}, {1u, 3, 24, 1, 1, 0, 1, 0}, {1u, 3, 24, 1, 1, 1, 1, 0}, {1u, 3, 24, 1, 1, 0, 2, 0},
+    {1u, 3, 32, 1, 1, 1, 2, 0}, {1u, 3, 48, 1, 1, 0, 1, 0}, {1u, 3, 48, 1, 1, 1, 1, 0}, {1u, 3, 48, 1, 1, 1, 2, 0},
+    {1u, 6, 8, 1, 1, 1, 2, 0}, {1u, 6, 12, 1, 1, 1, 1, 0}, {1u, 6, 16, 1, 1, 1, 1, 0}, {1u, 6, 24, 1, 1, 1, 1, 0},
+    {1u, 6, 32, 1, 1, 1, 1, 0}, {1u, 6, 32, 1, 1, 0, 2, 0}, {1u, 6, 48, 1, 1, 1, 2, 0},
+};
+constexpr bool packed_fma_build(uint32_t metric, int r, int nk, bool bf, bool ad, bool st, int occ, bool build) {
+    for (const PackedOptOut &o : kPackedOptOut)
+        if (o.metric == metric && o.r == r && o.nk == nk && o.bf == bf && o.ad == ad && o.st == st && o.occ == occ && o.build == build) return false;
+    return true;
+}
+
 // FMAs in the host SIMD order against the query staged in LDS (conflict-free: the 8 lanes of a group
 // read 128 contiguous bytes, the 8 groups broadcast), then the AVX reduction tree.
-template <uint32_t METRIC, int NK, int P, bool BF, int PMAX = P>
+template <uint32_t METRIC, int NK, int P, bool BF, int PMAX = P, bool PK = true>
 __device__ __forceinline__ void gather_consume(const DevIndex &ix, const float *qs, const Gather<NK, PMAX, BF> &g,
                                                const uint32_t (&node)[P], int slot, float qhdr,
                                                const float *qglobal, float (&out)[P]) {
-    float4 acc[P];
+    Acc4 acc[P];
 #pragma unroll
-    for (int p = 0; p < P; ++p) acc[p] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int p = 0; p < P; ++p) acc[p].lo = acc[p].hi = f2{0.f, 0.f};
     const float4 *qp = reinterpret_cast<const float4 *>(qs) + slot;
     if (!BF) {
 #pragma unroll
         for (int k = 0; k < NK; ++k) {
             const float4 qq = qp[k * 8];
+            const f2 ql = {qq.x, qq.y}, qh = {qq.z, qq.w};
 #pragma unroll
-            for (int p = 0; p < P; ++p) fma_chunk<METRIC>(acc[p], qq, g.x[p][k]);
+            for (int p = 0; p < P; ++p) {
+                const float4 xv = g.x[p][k];
+                fma_chunk<METRIC, PK>(acc[p], ql, qh, f2{xv.x, xv.y}, f2{xv.z, xv.w});
+            }
         }
     } else {
 #pragma unroll
         for (int m = 0; m < NK / 2; ++m) {
             const float4 q0 = qp[(2 * m) * 8], q1 = qp[(2 * m + 1) * 8];
+            const f2 q0l = {q0.x, q0.y}, q0h = {q0.z, q0.w}, q1l = {q1.x, q1.y}, q1h = {q1.z, q1.w};
 #pragma unroll
-            for (int p = 0; p < P; ++p) { // bf16 -> f32 is exact: the halfword becomes the high half of the word
+            for (int p = 0; p < P; ++p) {
                 const uint32_t w0 = __float_as_uint(g.x[p][BF ? m : 0].x), w1 = __float_as_uint(g.x[p][BF ? m : 0].y);
-                const float4 x0 = make_float4(__uint_as_float(w0 << 16), __uint_as_float(w0 & 0xFFFF0000u),
-                                              __uint_as_float(w1 << 16), __uint_as_float(w1 & 0xFFFF0000u));
-                fma_chunk<METRIC>(acc[p], q0, x0);
+                fma_chunk<METRIC, PK>(acc[p], q0l, q0h, bf16_pair_widen(w0), bf16_pair_widen(w1));
             }
 #pragma unroll
             for (int p = 0; p < P; ++p) {
                 const uint32_t w2 = __float_as_uint(g.x[p][BF ? m : 0].z), w3 = __float_as_uint(g.x[p][BF ? m : 0].w);
-                const float4 x1 = make_float4(__uint_as_float(w2 << 16), __uint_as_float(w2 & 0xFFFF0000u),
-                                              __uint_as_float(w3 << 16), __uint_as_float(w3 & 0xFFFF0000u));
-                fma_chunk<METRIC>(acc[p], q1, x1);
+                fma_chunk<METRIC, PK>(acc[p], q1l, q1h, bf16_pair_widen(w2), bf16_pair_widen(w3));
             }
         }
     }
 #pragma unroll
     for (int p = 0; p < P; ++p) {
-        float r = avx_tree_reduce(acc[p]);
+        float r = avx_tree_reduce(make_float4(acc[p].lo.x, acc[p].lo.y, acc[p].hi.x, acc[p].hi.y));
         if (METRIC == kCosine) {
             const uint32_t nd = node[p];
             r = cosine_finish_fn(r, qhdr, g.h[p], [&]() {
@@ -513,6 +576,7 @@ __device__ __forceinline__ void hnsw_wave_query(const HnswArgs &a, const uint32_
     // (profiles/r05b_ad_lanes_ab.log: 0.754 -> 0.673 ms per step; the squared-Euclidean build has no filter state and keeps two rows).
     // (bf16 rows widen every 16-byte piece to two float4 in front of the FMAs: their non-strict builds spill from 32 float4 per pass on)
     constexpr bool kWide2 = OCC == 1 || (2 * P * NL <= 48 && !kCosBfBig && !(AD && ((METRIC == kCosine && 2 * P * NL > 32) || (BF && 2 * P * NL >= 32))));
+    constexpr bool PK = packed_fma_build(METRIC, R, NK, BF, AD, ST, OCC, BUILD);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const DevIndex &ix = a.ix;
     const int lane = (int)threadIdx.x, grp = lane >> 3, j = lane & 7;
@@ -577,7 +641,7 @@ __device__ __forceinline__ void hnsw_wave_query(const HnswArgs &a, const uint32_
         }
         if constexpr (!GEN) {
             gather_issue<NK, W, BF, W, METRIC == kCosine>(ix, nd, slot, g);
-            gather_consume<METRIC, NK, W, BF>(ix, qs, g, nd, slot, qhdr, qglobal, o);
+            gather_consume<METRIC, NK, W, BF, W, PK>(ix, qs, g, nd, slot, qhdr, qglobal, o);
         }
 #pragma unroll
         for (int p = 0; p < W; ++p) {
@@ -615,7 +679,7 @@ __device__ __forceinline__ void hnsw_wave_query(const HnswArgs &a, const uint32_
             float o[1];
             Gather<NK, 1, BF> g;
             gather_issue<NK, 1, BF, 1, METRIC == kCosine>(ix, nd, slot, g);
-            gather_consume<METRIC, NK, 1, BF>(ix, qs, g, nd, slot, qhdr, qglobal, o);
+            gather_consume<METRIC, NK, 1, BF, 1, PK>(ix, qs, g, nd, slot, qhdr, qglobal, o);
             return __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(o[0]), 0));
         }
     };
@@ -652,6 +716,9 @@ __device__ __forceinline__ void hnsw_wave_query(const HnswArgs &a, const uint32_
             for (int k = 0; k < SL; ++k) x[p][k] = rp[k * 8];
         }
         __builtin_amdgcn_sched_barrier(0);
+        // Component-wise FMAs (the float4 fma_chunk), not the packed ones of the f32 passes: on register pairs this pass has a
+        // third fewer vector instructions and was SLOWER in the phase profile (visited+shadow 882 958 -> 904 276 cycles per query
+        // on one graph, counters equal: profiles/packed_fma_prof.log).
         float4 acc[W];
 #pragma unroll
         for (int p = 0; p < W; ++p) acc[p] = make_float4(0.f, 0.f, 0.f, 0.f);
