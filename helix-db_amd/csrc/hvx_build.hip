@@ -22,13 +22,16 @@
 // search builds for L2 / cosine + AVX+FMA + dim in {128,...,1536} + ef_construction <= 352, the GENERIC build of the same kernel
 // otherwise; select / link kernels per metric and tree), m0 <= 64 (m <= 32), ef_construction <= 800.  The kernels of THIS file hold one id
 // per lane and 64-bit masks: degree limits up to 32.  Limits up to 64 (the reference's scale fixture, M 32 / M0 64) run the kernels of
-// hvx_build_wide.hip -- two ids per lane, 128-bit masks, 128 search candidates per layer and node -- picked per index in insert_range;
+// hvx_build_wide.hip -- two ids per lane, 128-bit masks, 128 search candidates per layer and node;
 // their one-node steps are the two many-workgroup kernels of hvx_build_wide_seq.hip (f32 and bf16 rows; link_mode = 1: the one-wavefront
 // kernels); their batches hold half the fraction and do not overlap search and link.
 // bf16 images (hvx_index_build with dtype bf16, inserts, upserts, hvx_index_link_rows): the same loop over the packed rows.  The build search
 // takes the batch's rows widened to f32 as its queries (decode_rows_bf16_kernel), the BF builds of the select / link kernels widen bf16 rows
 // on their way into LDS (stage_row<BF>; build_link_wg_kernel<.., BF> in hvx_build_link_wg.h, instantiated in hvx_build_bf16.hip), the one-node
 // steps read them in place (pair_distance<.., BF>): every distance is the reference's on the ROUNDED vectors, bit for bit.
+// WHICH of these kernels a batch runs, with what grids and LDS, is decided on the host by plan_write_batch() in hvx_build_plan.h, next to the
+// degree limits and their defaults, the refusals, the link workgroups' geometry, the batch sizes and the scratch layout; insert_range below
+// is a loop over those plans and launch_write_batch the one switch that maps a plan to launches.
 // Round 3: the batched link step runs one WORKGROUP per link with the prune evaluated from LDS (build_link_wg_kernel below) and
 // the search side two wavefronts per SIMD for batches > 1 024 nodes: 1M x 768 in 4.1 s (round 2: 10.0 s).
 #include <hip/hip_runtime.h>
@@ -40,8 +43,7 @@
 
 #include "hvx_host.h"
 #include "hvx_graph_dev.h"
-#include "hvx_hnsw_plan.h"
-#include "hvx_build_dev.h"
+#include "hvx_build_plan.h"
 #include "hvx_build_link_wg.h"
 
 using namespace hvx;
@@ -195,12 +197,6 @@ template <uint32_t METRIC, bool FUSED, bool BF> __global__ __launch_bounds__(64)
 // Same distances, same comparisons, same order of decisions as the one-wavefront kernels: tests/test_gpu_build.py holds both to the oracle
 // row for row (hvx_build_params.link_mode = 1 selects the one-wavefront kernels).
 // ---------------------------------------------------------------------------------------------------------------------------------
-constexpr uint32_t kSeqRow = 35;                 // ids of a link's list (row + the node); wider rows take the one-wavefront kernel
-constexpr uint32_t kSeqRS = 36;                  // stride of a link's matrix: rows 0 .. nc (row nc: the owner's), columns 0 .. nc - 1
-constexpr uint32_t kSeqSelDm = 65 * 64;          // the select's matrix
-constexpr uint32_t kSeqLinkDm = kSeqRS * kSeqRS;
-constexpr uint32_t kSeqLayerDm = kSeqSelDm + 32u * kSeqLinkDm;
-constexpr uint32_t kSeqPairs = 128;              // (row, victim) removals one layer's links can log
 
 template <uint32_t METRIC, bool FUSED, bool BF> __global__ __launch_bounds__(256) void build_select_seq_kernel(BuildArgs a) {
     __shared__ uint32_t s_cid[64], s_wsc[128], s_last;
@@ -274,7 +270,6 @@ __device__ __forceinline__ SeqLds carve_seq(char *smem) {
     S.wsc = p;
     return S;
 }
-static size_t seq_lds_bytes() { return (size_t)(2 * 32 * kSeqRS + 5 * 32 + 2 * kSeqPairs + 36 + 16 * 128) * 4; }
 
 template <uint32_t METRIC, bool FUSED, bool BF> __global__ __launch_bounds__(1024) void build_link_seq_kernel(BuildArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -453,18 +448,12 @@ template <uint32_t METRIC, bool FUSED, bool BF> __global__ __launch_bounds__(102
     }
 }
 
-template <typename K> static hipError_t launch_build(K kern, dim3 grid, const BuildArgs &a, hipStream_t s) {
-    const size_t lds = build_lds_bytes(a.ix.ld);
-    hipLaunchKernelGGL(kern, grid, dim3(64), lds, s, a);
-    return hipGetLastError();
-}
-
-template <typename K> static hipError_t launch_link_wg(K kern, const BuildArgs &a, uint32_t layers, size_t lds, hipStream_t s) {
-    if (lds > 48 * 1024) { // (46 KB at <= 33 candidate rows: only larger Mmax would need it; the attribute is per function AND device)
-        const hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+template <typename K> static hipError_t launch_step(K kern, const StepGeom &g, const BuildArgs &a, hipStream_t s) {
+    if (g.lds > 48 * 1024) { // (46 KB at <= 33 candidate rows: only larger Mmax would need it; the attribute is per function AND device)
+        const hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(kern, dim3(a.b * 32u, layers), dim3(256), lds, s, a);
+    hipLaunchKernelGGL(kern, dim3(g.gx, g.gy), dim3(g.threads), g.lds, s, a);
     return hipGetLastError();
 }
 
@@ -514,10 +503,52 @@ static BuildKernels pick_build_kernels(uint32_t metric, bool fused, bool bf16 = 
     return fused ? build_kernels_of<kL1, true>() : build_kernels_of<kL1, false>();
 }
 
-} // namespace hvx
+// a device temporary that lives as long as its scope
+struct DevTemp {
+    void *p = nullptr;
+    DevTemp() = default;
+    DevTemp(const DevTemp &) = delete;
+    DevTemp &operator=(const DevTemp &) = delete;
+    ~DevTemp() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }
+    template <typename T> T *as() const { return static_cast<T *>(p); }
+};
 
-// hvx_build_params.sequential: HVX_BUILD_ONE_NODE (and any value the header does not name) = one node per batch
-static bool one_node_batches(const hvx_build_params *p) { return p->sequential != HVX_BUILD_AUTO && p->sequential != HVX_BUILD_BATCHED; }
+// the select and link launches of one batch, as planned (plan_write_batch, hvx_build_plan.h)
+static hipError_t launch_write_batch(const WriteBatchPlan &p, const WriteCtx &c, const BuildKernels &kern, BuildArgs ba, hipStream_t s) {
+    const bool fused = kernel_fused(ba.ix.fkernel);
+    hipError_t e = hipSuccess;
+    switch (p.select) {
+    case SelectStep::narrow_wave: e = launch_step(kern.select, p.sel, ba, s); break;
+    case SelectStep::narrow_eager:
+        ba.g0 = p.sel.g0; ba.gu = p.sel.gu;
+        hipLaunchKernelGGL(kern.select_seq, dim3(p.sel.gx), dim3(p.sel.threads), p.sel.lds, s, ba);
+        ba.g0 = p.lnk.g0; ba.gu = p.lnk.gu;
+        hipLaunchKernelGGL(kern.link_seq, dim3(p.lnk.gx), dim3(p.lnk.threads), p.lnk.lds, s, ba);
+        e = hipGetLastError();
+        break;
+    case SelectStep::wide_wave: e = launch_build_select_wide(ba, fused, c.bf16, dim3(p.sel.gx, p.sel.gy), s); break;
+    case SelectStep::wide_eager: // (both take their grids from wide_seq_geom, as the plan does)
+        e = launch_build_select_wide_seq(ba, fused, c.bf16, s);
+        if (e == hipSuccess) e = launch_build_link_wide_seq(ba, fused, c.bf16, s);
+        break;
+    }
+    if (e != hipSuccess) return e;
+    const LinkGeom &lg = p.link == LinkStep::wide_wg ? c.wide_link : c.link;
+    ba.ldp = lg.ldp;
+    ba.ncmax = lg.ncmax;
+    ba.link_ck = lg.link_ck;
+    switch (p.link) {
+    case LinkStep::none: break;
+    case LinkStep::narrow_wave: e = launch_step(kern.link, p.lnk, ba, s); break;
+    case LinkStep::narrow_wg: e = launch_step(kern.link_wg, p.lnk, ba, s); break;
+    case LinkStep::wide_wave: e = launch_build_link_wide(ba, fused, c.bf16, p.lnk.gx, s); break;
+    case LinkStep::wide_wg: e = launch_build_link_wide_wg(ba, fused, p.lnk.gy, p.lnk.lds, s); break;
+    }
+    return e;
+}
+
+} // namespace hvx
 
 extern "C" uint32_t hvx_index_last_write_path(const hvx_index *ix) { return ix ? ix->last_write_path : 0u; }
 extern "C" uint32_t hvx_index_last_write_tie_overflows(const hvx_index *ix) { return ix ? ix->last_write_tie_overflows : 0u; }
@@ -530,105 +561,79 @@ extern "C" void hvx_build_params_default(hvx_build_params *p) {
     p->batch_divisor = 32;
 }
 
-// insert_hnsw (mutation.rs:787-895) for the rows at insertion positions [first, first + count) of an image that already holds their
-// vectors, levels and (empty) neighbour rows: batches of nodes searched on the handle's stream while the previous batch is selected
-// and linked on a second one.  hvx_index_build runs it over a whole image (positions 0 .. n - 1, optionally scattered);
-// hvx_index_insert_batch over the rows it has just appended (id order).  levels_in[0] is the level of row level_row0.  Position p inserts row
-// (p * stride) mod `mod` (stride 1: row p).  The handle is private to the caller for the duration (its lock is held or it has not
-// been returned yet).
-static int insert_range(hvx_index *ix, uint64_t first, uint64_t count, const uint16_t *levels_in, uint64_t level_row0, const hvx_build_params *params,
-                        uint32_t stride, uint64_t mod, hvx_build_stats *stats, const float *build_q = nullptr) {
-    // build_q (bf16 images): the nodes' ROUNDED vectors as f32 [count][dim] on the device -- the queries of their build searches; null:
-    // every batch's rows are widened from the image into the call's scratch on the search stream
-    if (count == 0) return HVX_OK;
-    struct LevelOf { // levels_in[0] is the level of row level_row0
-        const uint16_t *p;
-        uint64_t r0;
-        explicit operator bool() const { return p != nullptr; }
-        uint16_t operator[](uint64_t row) const { return p[row - r0]; }
-    } levels{levels_in, level_row0};
-    const uint32_t m = ix->desc.m ? ix->desc.m : 16u;
-    const uint32_t m0 = std::max(ix->desc.m0 ? ix->desc.m0 : 2u * m, 2u * m);
-    const uint32_t efc = params->ef_construction ? params->ef_construction : 200u;
-    const uint32_t ef0 = std::max(efc, m0), efu = std::max(efc, 2u * m);
-    uint32_t bmax = params->max_batch ? params->max_batch : 2048u;
-    if (bmax > ix->max_batch) bmax = ix->max_batch; // per-batch scratch of the search kernel is sized by max_batch
-    const uint64_t rows_total = std::max<uint64_t>(first + count, mod);
-    auto row_at = [&](uint64_t pos) -> uint64_t { return stride == 1 ? pos : (pos * stride) % mod; };
+// a refusal of write_refusal() in the caller's words: "device build" "s", "device inserts" ""
+static int refuse_write(WriteRefusal r, const char *noun, const char *verb_s) {
+    switch (r) {
+    case kRefuseDegrees: return fail(HVX_ERR_UNSUPPORTED, "%s serve%s m0 <= 64 (m <= 32)", noun, verb_s);
+    case kRefuseRowsNarrow: return fail(HVX_ERR_UNSUPPORTED, "the image's neighbour rows are narrower than the degree limits (build it with hvx_index_build)");
+    case kRefuseRowsOver64: return fail(HVX_ERR_UNSUPPORTED, "%s with m0 > 32 serve%s neighbour rows of <= 64 ids", noun, verb_s);
+    case kRefuseEf: return fail(HVX_ERR_UNSUPPORTED, "device build serves ef_construction <= 800");
+    default: return HVX_OK;
+    }
+}
+
+// The rows an insert_range call links: insertion positions [first, first + count) of an image that already holds their vectors, levels
+// and (empty) neighbour rows.  Position p inserts row (p * stride) mod `mod` (stride 1: row p).
+struct WriteRows {
+    uint64_t first, count;
+    uint32_t stride;
+    uint64_t mod;
+    const uint16_t *levels; // levels[0] is the level of row level_row0; null: every node on layer 0 only
+    uint64_t level_row0;
+    // bf16 images: the nodes' ROUNDED vectors as f32 [count][dim] on the device -- the queries of their build searches; null: every
+    // batch's rows are widened from the image into the call's scratch on the search stream
+    const float *build_q;
+    uint64_t row_at(uint64_t pos) const { return stride == 1 ? pos : (pos * stride) % mod; }
+    uint16_t level_at(uint64_t pos) const { return levels ? levels[row_at(pos) - level_row0] : 0; }
+};
+
+// insert_hnsw (mutation.rs:787-895) for the rows of `r`: batches of nodes searched on the handle's stream while the previous batch is
+// selected and linked on a second one.  hvx_index_build runs it over a whole image (positions 0 .. n - 1, optionally scattered);
+// hvx_index_insert_batch over the rows it has just appended (id order).  Every batch runs what plan_write_batch (hvx_build_plan.h) says.
+// The handle is private to the caller for the duration (its lock is held or it has not been returned yet).
+static int insert_range(hvx_index *ix, const WriteRows &r, const hvx_build_params *params, hvx_build_stats *stats) {
+    if (r.count == 0) return HVX_OK;
+    const uint64_t first = r.first, end = r.first + r.count;
     DevIndex &d = ix->dev;
     uint32_t top_level = d.has_entry ? d.max_layer : 0u;
-    for (uint64_t p = first; p < first + count; ++p) top_level = std::max<uint32_t>(top_level, levels ? levels[row_at(p)] : 0);
+    for (uint64_t p = first; p < end; ++p) top_level = std::max<uint32_t>(top_level, r.level_at(p));
     HIP_TRY(hipSetDevice(ix->device));
     hipStream_t s = ix->stream;
     const uint32_t layers_max = top_level + 1u;
-    uint32_t *d_iota, *d_locks, *d_cnt, *d_sel, *d_selcnt, *d_status, *d_err, *d_tick;
-    uint64_t *d_cids;
-    float *d_csc, *d_gdm, *d_bq = nullptr;
+    const WriteCtx ctx = write_ctx(d, ix->desc, *params, ix->max_batch, layers_max);
+    const WriteDegrees &g = ctx.g;
+    // degree limits above 32: twice the candidates and selected neighbours per layer and node, and the kernels of hvx_build_wide.hip
+    const WriteRefusal refused = write_refusal(g, d.s0, d.su, kRefuseDegrees | (g.wide ? kRefuseRowsNarrow | kRefuseRowsOver64 : 0u));
+    if (refused == kRefuseDegrees) return refuse_write(refused, "device build", "s");
+    if (refused) return fail(HVX_ERR_UNSUPPORTED, "device build with m0 > 32 serves neighbour rows of m0 .. 64 ids");
     // Round 6: the scratch, the link stream and its events stay with the handle (a one-node insert / upsert paid nine hipMalloc + hipFree --
     // each a device synchronisation --, a stream and four events per call: ~2 ms of a 6.4-ms upsert).  Only tuning buffers are per call.
     // Round 4: the search of batch i + 1 runs on the handle's stream WHILE batch i is selected and linked on a second stream.  Batch i + 1
     // then does not see batch i -- which it tolerates exactly as the nodes of one batch tolerate not seeing each other: rows are only ever
     // read as stale-or-current (agent-scope stores by the link step, immutable vectors), never torn into invalid ids.  Candidate /
     // selection buffers are double-buffered; a promotion (new top layer = new entry point), a one-node batch and sequential mode do not overlap.
-    std::vector<void *> scratch;
-    auto salloc = [&](void **p, size_t bytes) -> int {
-        if (hipMalloc(p, std::max<size_t>(bytes, 16)) != hipSuccess) return fail(HVX_ERR_DEVICE, "hipMalloc(%zu) build scratch", bytes);
-        scratch.push_back(*p);
-        return HVX_OK;
-    };
-    auto release = [&]() { for (void *p : scratch) (void)hipFree(p); scratch.clear(); };
-    auto sbail = [&](int code) { // (a failed call may leave locks / tickets set: the next call starts from fresh scratch)
-        (void)hipStreamSynchronize(s);
-        release();
-        ix->ins_cap = 0;
-        ix->ins_locks_rows = 0;
-        return code;
-    };
-    if (std::max(m0, m) > 64u) return fail(HVX_ERR_UNSUPPORTED, "device build serves m0 <= 64 (m <= 32)");
-    if (std::max(m0, m) > 32u && (ix->dev.s0 > 64u || ix->dev.su > 64u || ix->dev.s0 < m0 || ix->dev.su < m))
-        return fail(HVX_ERR_UNSUPPORTED, "device build with m0 > 32 serves neighbour rows of m0 .. 64 ids");
-    // degree limits above 32: twice the candidates and selected neighbours per layer and node, and the kernels of hvx_build_wide.hip
-    const bool wide = std::max(m0, m) > 32u;
-    const uint32_t kc = wide ? kCandWide : kCand, selw = wide ? kSelWide : 32u;
-    const bool bf16 = d.dtype == HVX_BF16;
-    // ... whose one-node batches take the many-workgroup steps of hvx_build_wide_seq.hip wherever their geometry fits (rows <= 64 ids: above)
-    const bool wide_seq = wide && params->link_mode != 1u && wide_seq_geom(m, m0, layers_max).ok;
-    const size_t sz_cids = (size_t)layers_max * bmax * kc, sz_cnt = (size_t)layers_max * bmax, sz_sel = (size_t)layers_max * bmax * selw;
     int rc;
-    {
-        auto up = [](size_t b) { return (b + 255u) & ~(size_t)255u; };
-        const size_t b_iota = up(count * 4), b_cids = up(2 * sz_cids * 8), b_csc = up(2 * sz_cids * 4), b_cnt = up(2 * sz_cnt * 4), b_sel = up(2 * sz_sel * 4),
-                     b_status = up((size_t)bmax * 4), b_err = 256, b_tick = up(2 * 64 * 4),
-                     // the one-node steps' matrices: wide images by their geometry (a 129 x 128 select matrix and 64 link matrices on layer 0)
-                     b_gdm = up((wide_seq ? wide_seq_geom(m, m0, layers_max).total_floats() : (size_t)layers_max * kSeqLayerDm) * 4),
-                     b_bq = (bf16 && !build_q) ? up((size_t)bmax * d.dim * 4) : 0;
-        const size_t need = b_iota + b_cids + b_csc + 2 * b_cnt + b_sel + b_status + b_err + b_tick + b_gdm + b_bq;
-        if (need > ix->ins_cap) {
-            ix->ins_cap = 0;
-            if ((rc = ix->regrow(&ix->ins_scratch, need + need / 4))) return rc;
-            if (hipMemsetAsync(ix->ins_scratch, 0, need + need / 4, s) != hipSuccess) return fail(HVX_ERR_DEVICE, "memset");
-            ix->ins_cap = need + need / 4;
-        }
-        char *p = reinterpret_cast<char *>(ix->ins_scratch);
-        d_tick = reinterpret_cast<uint32_t *>(p); p += b_tick; // (first: zero between calls, set once by the memset above)
-        d_iota = reinterpret_cast<uint32_t *>(p); p += b_iota;
-        d_cids = reinterpret_cast<uint64_t *>(p); p += b_cids;
-        d_csc = reinterpret_cast<float *>(p); p += b_csc;
-        d_cnt = reinterpret_cast<uint32_t *>(p); p += b_cnt;
-        d_selcnt = reinterpret_cast<uint32_t *>(p); p += b_cnt;
-        d_sel = reinterpret_cast<uint32_t *>(p); p += b_sel;
-        d_status = reinterpret_cast<uint32_t *>(p); p += b_status;
-        d_err = reinterpret_cast<uint32_t *>(p); p += b_err;
-        d_gdm = reinterpret_cast<float *>(p); p += b_gdm;
-        if (b_bq) d_bq = reinterpret_cast<float *>(p);
-        const uint64_t lock_rows = std::max<uint64_t>(rows_total, ix->cap_rows);
-        if (lock_rows > ix->ins_locks_rows) { // one lock per row the image can hold: all zero between calls (every lock taken is released)
-            ix->ins_locks_rows = 0;
-            if ((rc = ix->regrow((void **)&ix->ins_locks, lock_rows * 4))) return rc;
-            if (hipMemsetAsync(ix->ins_locks, 0, lock_rows * 4, s) != hipSuccess) return fail(HVX_ERR_DEVICE, "memset");
-            ix->ins_locks_rows = lock_rows;
-        }
-        d_locks = ix->ins_locks;
+    const WriteScratch w = write_scratch(ctx, r.count, layers_max, d.dim, !r.build_q);
+    if (w.need > ix->ins_cap) {
+        ix->ins_cap = 0;
+        if ((rc = ix->regrow(&ix->ins_scratch, w.need + w.need / 4))) return rc;
+        if (hipMemsetAsync(ix->ins_scratch, 0, w.need + w.need / 4, s) != hipSuccess) return fail(HVX_ERR_DEVICE, "memset");
+        ix->ins_cap = w.need + w.need / 4;
+    }
+    char *const base = reinterpret_cast<char *>(ix->ins_scratch);
+    uint32_t *const d_tick = reinterpret_cast<uint32_t *>(base + w.tick), *const d_iota = reinterpret_cast<uint32_t *>(base + w.iota);
+    uint64_t *const d_cids = reinterpret_cast<uint64_t *>(base + w.cids);
+    float *const d_csc = reinterpret_cast<float *>(base + w.csc), *const d_gdm = reinterpret_cast<float *>(base + w.gdm);
+    uint32_t *const d_cnt = reinterpret_cast<uint32_t *>(base + w.cnt), *const d_selcnt = reinterpret_cast<uint32_t *>(base + w.selcnt);
+    uint32_t *const d_sel = reinterpret_cast<uint32_t *>(base + w.sel), *const d_status = reinterpret_cast<uint32_t *>(base + w.status);
+    uint32_t *const d_err = reinterpret_cast<uint32_t *>(base + w.err);
+    float *const d_bq = w.has_bq ? reinterpret_cast<float *>(base + w.bq) : nullptr;
+    const uint64_t lock_rows = std::max<uint64_t>(std::max<uint64_t>(end, r.mod), ix->cap_rows);
+    if (lock_rows > ix->ins_locks_rows) { // one lock per row the image can hold: all zero between calls (every lock taken is released)
+        ix->ins_locks_rows = 0;
+        if ((rc = ix->regrow((void **)&ix->ins_locks, lock_rows * 4))) return rc;
+        if (hipMemsetAsync(ix->ins_locks, 0, lock_rows * 4, s) != hipSuccess) return fail(HVX_ERR_DEVICE, "memset");
+        ix->ins_locks_rows = lock_rows;
     }
     if (!ix->ins_stream && hipStreamCreateWithFlags(&ix->ins_stream, hipStreamNonBlocking) != hipSuccess) return fail(HVX_ERR_DEVICE, "stream creation failed");
     for (int i = 0; i < 4; ++i)
@@ -636,80 +641,57 @@ static int insert_range(hvx_index *ix, uint64_t first, uint64_t count, const uin
     hipStream_t s2 = ix->ins_stream;
     hipEvent_t ev_search[2] = {ix->ins_ev[0], ix->ins_ev[1]}, ev_link[2] = {ix->ins_ev[2], ix->ins_ev[3]};
     bool link_pending[2] = {false, false};
-    auto drop_streams = [&]() { (void)hipStreamSynchronize(s2); };
-    auto sbail2 = [&](int code) { (void)hipStreamSynchronize(s); drop_streams(); return sbail(code); };
-    uint32_t *d_dbg = nullptr;
+    auto bail = [&](int code) { // (a failed call may leave locks / tickets set: the next call starts from fresh scratch)
+        (void)hipStreamSynchronize(s);
+        (void)hipStreamSynchronize(s2);
+        ix->ins_cap = 0;
+        ix->ins_locks_rows = 0;
+        return code;
+    };
+    DevTemp dbg;
     if (tuning_env("HVX_BUILD_DEBUG")) {
-        if ((rc = salloc((void **)&d_dbg, 32))) return sbail2(rc);
-        if (hipMemsetAsync(d_dbg, 0, 32, s) != hipSuccess) return sbail2(fail(HVX_ERR_DEVICE, "memset"));
+        if (dbg.alloc(32) != hipSuccess) return bail(fail(HVX_ERR_DEVICE, "hipMalloc(32) build scratch"));
+        if (hipMemsetAsync(dbg.p, 0, 32, s) != hipSuccess) return bail(fail(HVX_ERR_DEVICE, "memset"));
     }
-    hipLaunchKernelGGL(iota_kernel, dim3((uint32_t)((count + 255) / 256)), dim3(256), 0, s, d_iota, (uint32_t)count, (uint32_t)first, stride, (uint32_t)std::max<uint64_t>(mod, 1));
+    hipLaunchKernelGGL(iota_kernel, dim3((uint32_t)((r.count + 255) / 256)), dim3(256), 0, s, d_iota, (uint32_t)r.count, (uint32_t)first, r.stride, (uint32_t)std::max<uint64_t>(r.mod, 1));
     uint32_t *d_ties = d_err + 1; // nodes whose build search stayed flagged (the word next to the error word: one read for both)
-    if (hipMemsetAsync(d_err, 0, 8, s) != hipSuccess) return sbail2(fail(HVX_ERR_DEVICE, "memset"));
+    if (hipMemsetAsync(d_err, 0, 8, s) != hipSuccess) return bail(fail(HVX_ERR_DEVICE, "memset"));
 
-    uint32_t *l0w = const_cast<uint32_t *>(d.l0), *upw = const_cast<uint32_t *>(d.up);
-    const bool fused = kernel_fused(d.fkernel);
-    // build_link_wg_kernel: column blocks of <= 8 chunks (256 floats) of Mmax + 1 candidate rows and the owner's in LDS, row stride
-    // = 128 B mod 256 B (the eight row groups of a wavefront read different rows: conflict-free ds_read_b128 for neighbouring rows)
-    const uint32_t ncmax = std::max(m0, m) + 1u;
-    const uint32_t nk_rows = d.dim_main >> 5;
-    const uint32_t link_ck = std::min<uint32_t>(8u, (nk_rows + 1u) & ~1u);
-    const uint32_t ldp = link_ck * 32u + 32u;
-    const size_t link_lds = link_lds_bytes(ldp, ncmax);
-    // serves rows without a scalar tail (dim % 32 == 0, no padding) and <= 33 candidates (561 pairs = 4 wavefronts x 18 steps x 8)
-    const BuildKernels kern = pick_build_kernels(d.metric, fused, bf16);
-    const WideLinkGeom wgeo = wide ? wide_link_geom(d, m, m0) : WideLinkGeom{};
-    const bool link_wg_wide = wide && params->link_mode != 1u && wgeo.ok;
-    const bool link_wg = !wide && params->link_mode != 1u && kern.link_wg && !kernel_w4(d.fkernel) /* 32-lane tree only */ && ncmax <= 33u && nk_rows > 0 && d.dim_main == d.dim && d.ld == d.dim &&
-                         (bf16 ? d.dim % 64u == 0u /* a column block never splits a 16-byte piece */ && (size_t)(ncmax + 1u) * link_ck * 4u <= (size_t)kLinkPreBf16 * 256u : (size_t)(ncmax + 1u) * link_ck * 8u <= (size_t)kLinkPre * 256u);
-    const bool one_node = one_node_batches(params);
+    const BuildKernels kern = pick_build_kernels(d.metric, kernel_fused(d.fkernel), ctx.bf16);
     uint64_t done = first, batches = 0, singles = 0;
     if (!d.has_entry) { // the first node of an index: the entry point with empty rows on its layers (mutation.rs:706-739)
         d.has_entry = 1;
-        d.entry = (uint32_t)row_at(first);
-        d.max_layer = levels ? levels[row_at(first)] : 0;
+        d.entry = (uint32_t)r.row_at(first);
+        d.max_layer = r.level_at(first);
         done = first + 1;
         singles = 1;
     }
-    // (degree limits above 32: half the batch fraction -- a batch holds UP TO inserted / divisor nodes.  Nodes of a batch do not see each
-    // other, and at M 32 / M0 64 that costs more than the 0.01 of recall batching is granted: 8 000 x 128 Gaussian rows, divisor 16, ef 32:
-    // 0.8213 - 0.8240 against the sequential graph's 0.8326; with half the fraction 0.829)
-    const uint32_t divisor = (params->batch_divisor ? params->batch_divisor : 32u) * (wide ? 2u : 1u);
     bool prev_serial = true; // the previous batch must be complete before the next search starts
     // the iota / lock / err initialisation above ran on `s`: the link stream starts behind it
     if (hipEventRecord(ev_search[0], s) != hipSuccess || hipStreamWaitEvent(s2, ev_search[0], 0) != hipSuccess)
-        return sbail2(fail(HVX_ERR_DEVICE, "stream ordering failed"));
-    const uint64_t end = first + count;
+        return bail(fail(HVX_ERR_DEVICE, "stream ordering failed"));
     while (done < end) {
-        // batch = consecutive positions of the insertion order; a node above the current top layer is inserted alone and becomes the entry point
-        uint32_t bsz = 1;
-        const uint16_t lv0 = levels ? levels[row_at(done)] : 0;
+        const uint16_t lv0 = r.level_at(done);
         const bool promotes = lv0 > d.max_layer;
-        if (!promotes && !one_node) {
-            uint64_t want = std::min<uint64_t>(std::max<uint64_t>(done / divisor, 1), bmax);
-            want = std::min<uint64_t>(want, end - done);
-            while (bsz < want && !((levels ? levels[row_at(done + bsz)] : 0) > d.max_layer)) ++bsz;
-        }
+        const uint32_t bsz = write_batch_size(ctx, done, end, promotes, [&](uint64_t pos) { return r.level_at(pos) > d.max_layer; });
+        const uint32_t layers = d.max_layer + 1u; // old max_layer + 1
+        const WriteBatchPlan plan = plan_write_batch(ctx, bsz, promotes, layers);
         const uint32_t pb = (uint32_t)(batches & 1u); // buffer set of this batch
-        // (degree limits above 32 do not overlap either: at M 32 / M0 64 a batch that sees neither its own nodes nor the batch before it
-        // costs 0.002 of recall@10 at ef 32 on 8 000 Gaussian rows -- 0.8216 against 0.8235 --, a fifth of the margin batching is granted)
-        const bool serial = promotes || bsz == 1u || one_node || params->link_mode == 1u || wide;
         // the buffers of set pb were last read by the link step of batch - 2; and a serial batch (or the batch behind one) starts
         // only when everything before it is in the graph
-        if (link_pending[pb] && hipStreamWaitEvent(s, ev_link[pb], 0) != hipSuccess) return sbail2(fail(HVX_ERR_DEVICE, "stream ordering failed"));
-        if ((serial || prev_serial) && link_pending[pb ^ 1u] && hipStreamWaitEvent(s, ev_link[pb ^ 1u], 0) != hipSuccess)
-            return sbail2(fail(HVX_ERR_DEVICE, "stream ordering failed"));
-        const uint32_t layers = d.max_layer + 1u; // old max_layer + 1
-        uint64_t *b_cids = d_cids + (size_t)pb * sz_cids;
-        float *b_csc = d_csc + (size_t)pb * sz_cids;
-        uint32_t *b_cnt = d_cnt + (size_t)pb * sz_cnt, *b_sel = d_sel + (size_t)pb * sz_sel, *b_selcnt = d_selcnt + (size_t)pb * sz_cnt;
+        if (link_pending[pb] && hipStreamWaitEvent(s, ev_link[pb], 0) != hipSuccess) return bail(fail(HVX_ERR_DEVICE, "stream ordering failed"));
+        if ((plan.serial || prev_serial) && link_pending[pb ^ 1u] && hipStreamWaitEvent(s, ev_link[pb ^ 1u], 0) != hipSuccess)
+            return bail(fail(HVX_ERR_DEVICE, "stream ordering failed"));
+        uint64_t *b_cids = d_cids + (size_t)pb * w.sz_cids;
+        float *b_csc = d_csc + (size_t)pb * w.sz_cids;
+        uint32_t *b_cnt = d_cnt + (size_t)pb * w.sz_cnt, *b_sel = d_sel + (size_t)pb * w.sz_sel, *b_selcnt = d_selcnt + (size_t)pb * w.sz_cnt;
         HnswArgs a{};
         a.ix = d;
         a.bitmap = ix->d_bitmap;
         a.words_per_query = ix->words_per_query;
-        a.k = kc; // the first 2 * Mmax entries of W (mutation.rs:1072-1097)
-        a.ef = ef0;
-        a.build_ef_upper = efu;
+        a.k = g.kc; // the first 2 * Mmax entries of W (mutation.rs:1072-1097)
+        a.ef = g.ef0;
+        a.build_ef_upper = g.efu;
         a.out_ids = b_cids;
         a.out_scores = b_csc;
         a.out_counts = b_cnt;
@@ -717,22 +699,21 @@ static int insert_range(hvx_index *ix, uint64_t first, uint64_t count, const uin
         a.tie_flags = ix->d_tie;
         a.tie_count = d_ties; // (a flagged build search is counted, never repeated: hvx_index_last_write_tie_overflows)
         a.build_nodes = d_iota + (done - first);
-        if (bf16 && build_q) a.queries = build_q + (size_t)(done - first) * d.dim;
-        else if (bf16) {
+        if (ctx.bf16 && r.build_q) a.queries = r.build_q + (size_t)(done - first) * d.dim;
+        else if (ctx.bf16) {
             hipLaunchKernelGGL(decode_rows_bf16_kernel, dim3((uint32_t)(((size_t)bsz * (d.dim >> 3) + 255u) / 256u)), dim3(256), 0, s, d.vecb, d_iota + (done - first), bsz, d.dim, d_bq);
-            if (hipGetLastError() != hipSuccess) return sbail2(fail(HVX_ERR_DEVICE, "launch of the bf16 query rows failed"));
+            if (hipGetLastError() != hipSuccess) return bail(fail(HVX_ERR_DEVICE, "launch of the bf16 query rows failed"));
             a.queries = d_bq;
         }
-        // more nodes than SIMDs: two searches per SIMD instead of two rounds (bf16 rows: the build search exists one per SIMD only)
-        a.occupancy = (bsz > 1024u && params->link_mode != 1u && !bf16) ? 2 : 1;
-        if (launch_hnsw_wave(a, bsz, s) != hipSuccess) return sbail2(fail(HVX_ERR_DEVICE, "build search launch failed: %s", hipGetErrorString(hipGetLastError())));
+        a.occupancy = plan.occupancy;
+        if (launch_hnsw_wave(a, bsz, s) != hipSuccess) return bail(fail(HVX_ERR_DEVICE, "build search launch failed: %s", hipGetErrorString(hipGetLastError())));
         if (hipEventRecord(ev_search[pb], s) != hipSuccess || hipStreamWaitEvent(s2, ev_search[pb], 0) != hipSuccess)
-            return sbail2(fail(HVX_ERR_DEVICE, "stream ordering failed"));
+            return bail(fail(HVX_ERR_DEVICE, "stream ordering failed"));
         BuildArgs ba{};
         ba.ix = d;
-        ba.l0 = l0w;
-        ba.up = upw;
-        ba.locks = d_locks;
+        ba.l0 = const_cast<uint32_t *>(d.l0);
+        ba.up = const_cast<uint32_t *>(d.up);
+        ba.locks = ix->ins_locks;
         ba.nodes = d_iota + (done - first);
         ba.b = bsz;
         ba.layers = layers;
@@ -741,99 +722,81 @@ static int insert_range(hvx_index *ix, uint64_t first, uint64_t count, const uin
         ba.cand_cnt = b_cnt;
         ba.sel = b_sel;
         ba.sel_cnt = b_selcnt;
-        ba.m = m;
-        ba.m0 = m0;
+        ba.m = g.m;
+        ba.m0 = g.m0;
         ba.err = d_err;
-        ba.dbg = d_dbg;
-        ba.kc = kc;
-        ba.selw = selw;
-        // one node: its select and its links as two many-workgroup steps with every prune's distance matrix evaluated up front
-        const bool seq_step = !wide && bsz == 1u && params->link_mode != 1u && d.s0 + 1u <= kSeqRow && d.su + 1u <= kSeqRow;
-        hipError_t e;
-        uint32_t path = wide ? HVX_WRITE_WIDE : 0u; // hvx_index_last_write_path
-        if (wide && bsz == 1u && wide_seq) { // two ids per lane, one node: select and links as two many-workgroup steps (f32 and bf16 rows)
-            ba.gdm = d_gdm;
-            ba.tick = d_tick;
-            e = launch_build_select_wide_seq(ba, fused, bf16, s2);
-            if (e == hipSuccess) e = launch_build_link_wide_seq(ba, fused, bf16, s2);
-            path |= HVX_WRITE_EAGER_STEPS;
-        } else if (wide) { // the one-wavefront kernels for one node (link_mode = 1), one workgroup per link for a batch
-            e = launch_build_select_wide(ba, fused, bf16, dim3(bsz, layers), s2);
-            if (e == hipSuccess) {
-                // The workgroup kernel reads 2 145 pairs x dim out of LDS per link: LDS-bandwidth bound, ~48 us per link at dim 768 with one
-                // workgroup per CU.  Once a batch has enough nodes for the one-wavefront kernel's dependent gathers to overlap across nodes
-                // (>= 1 024: four wavefronts per CU) that kernel is the faster link step -- 1M x 768, batches of 2 048: 13.9 s against 15.9 s --,
-                // below that the workgroup kernel is (8 000 x 128, batches <= 250: 0.22 s against 0.99 s).
-                constexpr uint32_t kWideWgMaxBatch = 1024;
-                if (bsz > 1u && bsz < kWideWgMaxBatch && link_wg_wide) { // (f32 rows: wide_link_geom; a bf16 batch of any size takes the one-wavefront kernel)
-                    ba.ldp = wgeo.ldp;
-                    ba.ncmax = wgeo.ncmax;
-                    ba.link_ck = wgeo.link_ck;
-                    e = launch_build_link_wide_wg(ba, fused, layers, wgeo.lds, s2);
-                    path |= HVX_WRITE_LINK_WG;
-                } else {
-                    e = launch_build_link_wide(ba, fused, bf16, bsz, s2);
-                    path |= HVX_WRITE_ONE_WAVE;
-                }
-            }
-        } else if (seq_step) {
-            ba.gdm = d_gdm;
-            ba.tick = d_tick;
-            ba.g0 = 63u; ba.gu = 16u; // 32 row groups per workgroup: 2 016 pairs among 64 candidates on layer 0, 496 among 32 above
-            hipLaunchKernelGGL(kern.select_seq, dim3(ba.g0 + (layers - 1u) * ba.gu), dim3(256), 0, s2, ba);
-            ba.g0 = 96u; ba.gu = 12u; // 128 row groups per workgroup: <= 32 links x 561 pairs on layer 0, <= 16 x 153 above
-            hipLaunchKernelGGL(kern.link_seq, dim3(ba.g0 + (layers - 1u) * ba.gu), dim3(1024), seq_lds_bytes(), s2, ba);
-            e = hipGetLastError();
-            path |= HVX_WRITE_EAGER_STEPS;
-        } else {
-            e = launch_build(kern.select, dim3(bsz, layers), ba, s2);
-        }
-        if (e == hipSuccess && !seq_step && !wide) {
-            if (bsz > 1u && link_wg) { // batched mode: one workgroup per link, prunes evaluated from LDS
-                ba.ldp = ldp;
-                ba.ncmax = ncmax;
-                ba.link_ck = link_ck;
-                e = launch_link_wg(kern.link_wg, ba, layers, link_lds, s2);
-                path |= HVX_WRITE_LINK_WG;
-            } else { // one node (the reference's order exactly), or rows the workgroup kernel does not serve: one wavefront per node
-                e = launch_build(kern.link, dim3(bsz), ba, s2);
-                path |= HVX_WRITE_ONE_WAVE;
-            }
-        }
-        ix->last_write_path |= path;
-        if (e != hipSuccess) return sbail2(fail(HVX_ERR_DEVICE, "build launch failed: %s", hipGetErrorString(e)));
-        if (hipEventRecord(ev_link[pb], s2) != hipSuccess) return sbail2(fail(HVX_ERR_DEVICE, "stream ordering failed"));
+        ba.dbg = dbg.as<uint32_t>();
+        ba.gdm = d_gdm;
+        ba.tick = d_tick;
+        ba.kc = g.kc;
+        ba.selw = g.selw;
+        const hipError_t e = launch_write_batch(plan, ctx, kern, ba, s2);
+        ix->last_write_path |= plan.path;
+        if (e != hipSuccess) return bail(fail(HVX_ERR_DEVICE, "build launch failed: %s", hipGetErrorString(e)));
+        if (hipEventRecord(ev_link[pb], s2) != hipSuccess) return bail(fail(HVX_ERR_DEVICE, "stream ordering failed"));
         link_pending[pb] = true;
-        prev_serial = serial;
+        prev_serial = plan.serial;
         if (promotes) { // mutation.rs:769-772
-            d.entry = (uint32_t)row_at(done);
+            d.entry = (uint32_t)r.row_at(done);
             d.max_layer = lv0;
         }
         done += bsz;
         batches += 1;
         singles += bsz == 1 ? 1 : 0;
         if ((batches & 63u) == 0u && (hipStreamSynchronize(s) != hipSuccess || hipStreamSynchronize(s2) != hipSuccess)) // bound the launch queues
-            return sbail2(fail(HVX_ERR_DEVICE, "build kernels failed: %s", hipGetErrorString(hipGetLastError())));
+            return bail(fail(HVX_ERR_DEVICE, "build kernels failed: %s", hipGetErrorString(hipGetLastError())));
     }
-    if (hipStreamSynchronize(s2) != hipSuccess) return sbail2(fail(HVX_ERR_DEVICE, "build did not complete: %s", hipGetErrorString(hipGetLastError())));
-    drop_streams();
+    if (hipStreamSynchronize(s2) != hipSuccess) return bail(fail(HVX_ERR_DEVICE, "build did not complete: %s", hipGetErrorString(hipGetLastError())));
     uint32_t words[2] = {0u, 0u}; // the error word, the flagged nodes
     if (hipMemcpyAsync(words, d_err, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return sbail(fail(HVX_ERR_DEVICE, "build did not complete: %s", hipGetErrorString(hipGetLastError())));
-    const uint32_t err = words[0];
+        return bail(fail(HVX_ERR_DEVICE, "build did not complete: %s", hipGetErrorString(hipGetLastError())));
     ix->last_write_tie_overflows += words[1];
-    if (d_dbg) {
+    if (dbg.p) {
         uint32_t h[8] = {0};
-        (void)hipMemcpy(h, d_dbg, 32, hipMemcpyDeviceToHost);
+        (void)hipMemcpy(h, dbg.p, 32, hipMemcpyDeviceToHost);
         fprintf(stderr, "[hvx build] link step: lock spins %u, prunes %u, reverse-edge removals %u, plain appends %u\n", h[0], h[1], h[2], h[3]);
     }
-    release();
-    if (err) return fail(HVX_ERR_INVARIANT, "a neighbour row overflowed its stride during the build");
+    if (words[0]) return fail(HVX_ERR_INVARIANT, "a neighbour row overflowed its stride during the build");
     if (stats) {
         stats->batches += batches;
         stats->single_node_batches += singles;
-        stats->nodes += count;
+        stats->nodes += r.count;
     }
+    return HVX_OK;
+}
+
+// a completed write becomes the handle's description and the image's visible generation
+static void publish_write(hvx_index *ix, bool bump = true) {
+    ix->desc.has_entry = 1;
+    ix->desc.entry_point = ix->ids_ref()[ix->dev.entry];
+    ix->desc.max_layer = ix->dev.max_layer;
+    ix->publish_view(bump);
+}
+
+// Rows on their way into an image: `count` rows of `vectors` (row stride dim) are uploaded to vdst with the image's ld (zero padded),
+// rounded in place for bf16 images (the index IS the rounded vectors: validation and headers see them) and validated as rows of the image,
+// their headers written to hdr_dst.  The first invalid row fails the call with its status (mutation.rs:660-690).  Waits for the stream.
+static int stage_rows(hvx_index *ix, const float *vectors, const uint64_t *node_ids, uint32_t count, float *vdst, float *hdr_dst) {
+    const DevIndex &d = ix->dev;
+    hipStream_t s = ix->stream;
+    if (d.ld == d.dim) {
+        HIP_TRY(hipMemcpyAsync(vdst, vectors, (size_t)count * d.dim * 4, hipMemcpyDefault, s));
+    } else {
+        HIP_TRY(hipMemsetAsync(vdst, 0, (size_t)count * d.ld * 4, s));
+        HIP_TRY(hipMemcpy2DAsync(vdst, (size_t)d.ld * 4, vectors, (size_t)d.dim * 4, (size_t)d.dim * 4, count, hipMemcpyDefault, s));
+    }
+    if (d.dtype == HVX_BF16) HIP_TRY(launch_round_bf16_inplace(vdst, (size_t)count * d.ld, s));
+    DevTemp status;
+    HIP_TRY(status.alloc((size_t)count * 4));
+    std::vector<uint32_t> st(count);
+    DevIndex view = d;
+    view.vec = vdst;
+    hipError_t e = launch_validate_rows(view, count, ix->limit, status.as<uint32_t>(), hdr_dst, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(st.data(), status.p, (size_t)count * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(HVX_ERR_DEVICE, "row validation: %s", hipGetErrorString(e));
+    for (uint32_t i = 0; i < count; ++i)
+        if (st[i]) return fail((int)st[i], "vector of node %llu is invalid for this metric (status %u)", (unsigned long long)node_ids[i], st[i]);
     return HVX_OK;
 }
 
@@ -843,27 +806,25 @@ extern "C" int hvx_index_build(const hvx_index_desc *desc, const uint64_t *node_
     *out = nullptr;
     const uint64_t n = desc->n;
     if (n && (!node_ids || !vectors)) return fail(HVX_ERR_INVARIANT, "null array");
-    const uint32_t m = desc->m ? desc->m : 16u;
-    const uint32_t m0 = std::max(desc->m0 ? desc->m0 : 2u * m, 2u * m); // MutationDegreeLimits (mutation.rs:178-196)
-    const uint32_t efc = params->ef_construction ? params->ef_construction : 200u;
+    const WriteDegrees g = write_degrees(*desc, params);
     if (desc->dtype != HVX_F32 && desc->dtype != HVX_BF16)
         return fail(HVX_ERR_UNSUPPORTED, "the device build reads f32 and bf16 rows (import the built graph with dtype fp8 afterwards)");
-    if (m0 > 64u || m > 32u) return fail(HVX_ERR_UNSUPPORTED, "device build serves m0 <= 64 (m <= 32)");
+    const WriteRefusal refused = write_refusal(g, 0u, 0u, kRefuseDegrees | kRefuseEf);
+    if (refused == kRefuseDegrees) return refuse_write(refused, "device build", "s");
     if (desc->dtype == HVX_BF16) { // what the bf16 import and the unrolled build search over bf16 rows serve
         const uint32_t nk = desc->dim >> 5;
         const bool dim_ok = desc->dim % 32u == 0u && (nk == 4 || nk == 8 || nk == 12 || nk == 16 || nk == 24 || nk == 32 || nk == 48);
         if (!dim_ok || desc->float_kernel != HVX_KERNEL_AVX_FMA || (desc->metric != HVX_L2_SQUARED && desc->metric != HVX_COSINE_HALF))
             return fail(HVX_ERR_UNSUPPORTED, "the device build over bf16 rows serves L2 / cosine, the AVX+FMA summation tree and dim in {128, 256, 384, 512, 768, 1024, 1536}");
-        if (wave_build_need(std::max(efc, m0), std::max(efc, 2u * m)) > kBeamNarrowMax)
+        if (wave_build_need(g.ef0, g.efu) > kBeamNarrowMax)
             return fail(HVX_ERR_UNSUPPORTED, "the device build over bf16 rows serves max(ef_construction, m0, 2 m) <= %u", kBeamNarrowMax - kBeamSlack);
     }
-    if (wave_build_need(std::max(efc, m0), std::max(efc, 2u * m)) > kBeamMax) return fail(HVX_ERR_UNSUPPORTED, "device build serves ef_construction <= 800");
-    const uint32_t ef0 = std::max(efc, m0);
+    if (refused) return refuse_write(refused, "device build", "s");
 
     // ---- the image: rows + EMPTY graph with rows sized for m0 / m (+ room for rows appended later: hvx_index_insert_batch) ----
     hvx_index_desc d0 = *desc;
-    d0.m = m;
-    d0.m0 = m0;
+    d0.m = g.m;
+    d0.m0 = g.m0;
     d0.has_entry = 0;
     d0.max_layer = 0;
     if (d0.max_batch == 0) d0.max_batch = 1024;
@@ -876,11 +837,11 @@ extern "C" int hvx_index_build(const hvx_index_desc *desc, const uint64_t *node_
     std::vector<uint64_t> zeros0(n + 1, 0), zerosu(up_rows + 1, 0);
     uint64_t dummy = 0;
     hvx_index *ix = nullptr;
-    int rc = import_index(&d0, node_ids, vectors, zeros0.data(), &dummy, levels, zerosu.data(), &dummy, m0, m, &ix, params->reserve_rows,
+    int rc = import_index(&d0, node_ids, vectors, zeros0.data(), &dummy, levels, zerosu.data(), &dummy, g.m0, g.m, &ix, params->reserve_rows,
                           params->reserve_upper_rows);
     if (rc) return rc;
     auto bail = [&](int code) { hvx_index_free(ix); return code; };
-    if (!hnsw_wave_build_supported(ix->dev, ef0, std::max(efc, 2u * m)))
+    if (!hnsw_wave_build_supported(ix->dev, g.ef0, g.efu))
         return bail(fail(HVX_ERR_UNSUPPORTED, "device build serves neighbour rows of <= 64 ids"));
     if (stats) memset(stats, 0, sizeof(*stats));
     if (n == 0) { *out = ix; return HVX_OK; }
@@ -894,11 +855,8 @@ extern "C" int hvx_index_build(const hvx_index_desc *desc, const uint64_t *node_
         while (st > 1 && gcd(st, n) != 1) --st;
         stride = (uint32_t)std::max<uint64_t>(st, 1);
     }
-    if ((rc = insert_range(ix, 0, n, levels, 0, params, stride, n, stats))) return bail(rc);
-    ix->desc.has_entry = 1;
-    ix->desc.entry_point = node_ids[ix->dev.entry];
-    ix->desc.max_layer = ix->dev.max_layer;
-    ix->publish_view(/*bump=*/false); // generation 1 = the built image (import_index published the empty graph under the same number)
+    if ((rc = insert_range(ix, WriteRows{0, n, stride, n, levels, 0, nullptr}, params, stats))) return bail(rc);
+    publish_write(ix, /*bump=*/false); // generation 1 = the built image (import_index published the empty graph under the same number)
     *out = ix;
     return HVX_OK;
 }
@@ -932,13 +890,9 @@ extern "C" int hvx_index_insert_batch(hvx_index *ix, const uint64_t *node_ids, c
         one.sequential = HVX_BUILD_ONE_NODE;
         params = &one;
     }
-    const uint32_t m = ix->desc.m ? ix->desc.m : 16u;
-    const uint32_t m0 = std::max(ix->desc.m0 ? ix->desc.m0 : 2u * m, 2u * m);
-    const uint32_t efc = params->ef_construction ? params->ef_construction : 200u;
-    if (m0 > 64u || m > 32u) return fail(HVX_ERR_UNSUPPORTED, "device inserts serve m0 <= 64 (m <= 32)");
-    if (d.s0 < m0 || d.su < m) return fail(HVX_ERR_UNSUPPORTED, "the image's neighbour rows are narrower than the degree limits (build it with hvx_index_build)");
-    if (m0 > 32u && (d.s0 > 64u || d.su > 64u)) return fail(HVX_ERR_UNSUPPORTED, "device inserts with m0 > 32 serve neighbour rows of <= 64 ids");
-    if (wave_build_need(std::max(efc, m0), std::max(efc, 2u * m)) > kBeamMax) return fail(HVX_ERR_UNSUPPORTED, "device build serves ef_construction <= 800");
+    const WriteDegrees g = write_degrees(ix->desc, params);
+    if (const WriteRefusal refused = write_refusal(g, d.s0, d.su, kRefuseDegrees | kRefuseRowsNarrow | kRefuseRowsOver64 | kRefuseEf))
+        return refuse_write(refused, "device inserts", "");
     const uint64_t n0 = d.n;
     if (n0 + count > ix->cap_rows)
         return fail(HVX_ERR_CANDIDATE_LIMIT, "the image holds %llu of %llu rows: %u more do not fit (hvx_build_params.reserve_rows)", (unsigned long long)n0,
@@ -956,7 +910,7 @@ extern "C" int hvx_index_insert_batch(hvx_index *ix, const uint64_t *node_ids, c
         return fail(HVX_ERR_CANDIDATE_LIMIT, "the image's upper-layer rows are exhausted (%llu + %llu > %llu: hvx_build_params.reserve_upper_rows)",
                     (unsigned long long)ix->up_rows_used, (unsigned long long)up_need, (unsigned long long)ix->cap_up_rows);
     // (a bf16 image outside the unrolled shapes has no build search either: that one fails at its launch)
-    if (!hnsw_wave_build_supported(d, std::max(efc, m0), std::max(efc, 2u * m)) && (d.s0 > 64u || d.su > 64u)) return fail(HVX_ERR_UNSUPPORTED, "device build serves neighbour rows of <= 64 ids");
+    if (!hnsw_wave_build_supported(d, g.ef0, g.efu) && (d.s0 > 64u || d.su > 64u)) return fail(HVX_ERR_UNSUPPORTED, "device build serves neighbour rows of <= 64 ids");
     hipStream_t s = ix->stream;
     // ---- the rows: upload into the spare capacity, validate, headers (nothing is visible yet: d.n still ends before them) ----
     float *vdst;
@@ -971,27 +925,8 @@ extern "C" int hvx_index_insert_batch(hvx_index *ix, const uint64_t *node_ids, c
     } else {
         vdst = const_cast<float *>(d.vec) + (size_t)n0 * d.ld;
     }
-    if (d.ld == d.dim) {
-        HIP_TRY(hipMemcpyAsync(vdst, vectors, (size_t)count * d.dim * 4, hipMemcpyDefault, s));
-    } else {
-        HIP_TRY(hipMemsetAsync(vdst, 0, (size_t)count * d.ld * 4, s));
-        HIP_TRY(hipMemcpy2DAsync(vdst, (size_t)d.ld * 4, vectors, (size_t)d.dim * 4, (size_t)d.dim * 4, count, hipMemcpyDefault, s));
-    }
-    if (bf16) HIP_TRY(launch_round_bf16_inplace(vdst, (size_t)count * d.ld, s)); // the index IS the rounded vectors
-    uint32_t *d_rowstatus = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_rowstatus, (size_t)count * 4));
-    {
-        DevIndex view = d;
-        view.vec = vdst;
-        std::vector<uint32_t> st(count);
-        hipError_t e = launch_validate_rows(view, count, ix->limit, d_rowstatus, const_cast<float *>(d.hdr) + n0, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(st.data(), d_rowstatus, (size_t)count * 4, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        (void)hipFree(d_rowstatus);
-        if (e != hipSuccess) return fail(HVX_ERR_DEVICE, "row validation: %s", hipGetErrorString(e));
-        for (uint32_t i = 0; i < count; ++i)
-            if (st[i]) return fail((int)st[i], "vector of node %llu is invalid for this metric (status %u)", (unsigned long long)node_ids[i], st[i]);
-    }
+    int rc = stage_rows(ix, vectors, node_ids, count, vdst, const_cast<float *>(d.hdr) + n0);
+    if (rc) return rc;
     // ---- levels, upper-row bases, ids ----
     std::vector<uint16_t> h_lv(count, 0);
     std::vector<uint32_t> h_base(count, kSentinel);
@@ -1020,13 +955,10 @@ extern "C" int hvx_index_insert_batch(hvx_index *ix, const uint64_t *node_ids, c
     ix->desc.n = d.n;
     ix->up_rows_used = r;
     // ---- link them into the graph ----
-    int rc = insert_range(ix, n0, count, h_lv.data(), n0, params, 1u, 0, stats, bf16 ? vdst : nullptr);
+    rc = insert_range(ix, WriteRows{n0, count, 1u, 0, h_lv.data(), n0, bf16 ? vdst : nullptr}, params, stats);
     if (rc) return rc; // (the image is partially linked: the host discards the handle and re-hydrates)
-    ix->desc.has_entry = 1;
-    ix->desc.entry_point = ix->ids_ref()[d.entry];
-    ix->desc.max_layer = d.max_layer;
     ix->desc.shard_id_hi = ix->ids_ref()[d.n - 1];
-    ix->publish_view();
+    publish_write(ix);
     return HVX_OK;
 }
 
@@ -1049,53 +981,35 @@ extern "C" int hvx_index_upsert_batch(hvx_index *ix, const uint64_t *node_ids, c
     if (stats) memset(stats, 0, sizeof(*stats));
     if (count == 0) { ix->last_write_path = 0u; ix->last_write_tie_overflows = 0u; return HVX_OK; }
     if (ix->is_fork) return fail(HVX_ERR_UNSUPPORTED, "rows are written through the handle that owns the image, not a fork");
-    const uint32_t dim = ix->dev.dim, ld = ix->dev.ld;
+    const uint32_t ld = ix->dev.ld;
     if (ix->dev.dtype != HVX_F32 && ix->dev.dtype != HVX_BF16) return fail(HVX_ERR_UNSUPPORTED, "rows are written into f32 and bf16 images");
     const bool bf16 = ix->dev.dtype == HVX_BF16; // (round 6: an id the image holds gets its new vector in its slot; bf16 images have no spare rows to append to)
-    { // the insert half's degree limits, before the delete half changes anything
-        const uint32_t m = ix->desc.m ? ix->desc.m : 16u;
-        const uint32_t m0 = std::max(ix->desc.m0 ? ix->desc.m0 : 2u * m, 2u * m);
-        if (m0 > 64u || m > 32u) return fail(HVX_ERR_UNSUPPORTED, "device upserts serve m0 <= 64 (m <= 32)");
-        if (m0 > 32u && (ix->dev.s0 > 64u || ix->dev.su > 64u)) return fail(HVX_ERR_UNSUPPORTED, "device upserts with m0 > 32 serve neighbour rows of <= 64 ids");
-    }
+    // the insert half's degree limits, before the delete half changes anything
+    if (const WriteRefusal refused = write_refusal(write_degrees(ix->desc, &seq), ix->dev.s0, ix->dev.su, kRefuseDegrees | kRefuseRowsOver64))
+        return refuse_write(refused, "device upserts", "");
     // ---- every vector is validated before anything changes (an invalid one fails the call: mutation.rs:660-690) ----
-    float *d_tmp = nullptr, *d_tmph = nullptr;
-    uint32_t *d_st = nullptr;
+    DevTemp tmp; // the validated (bf16 images: rounded) vectors, row stride ld
     {
         std::lock_guard<std::mutex> lock(ix->mu);
         HIP_TRY(hipSetDevice(ix->device));
-        hipStream_t s = ix->stream;
-        if (hipMalloc((void **)&d_tmp, (size_t)count * ld * 4) != hipSuccess || hipMalloc((void **)&d_tmph, (size_t)count * 4) != hipSuccess ||
-            hipMalloc((void **)&d_st, (size_t)count * 4) != hipSuccess) {
-            (void)hipFree(d_tmp); (void)hipFree(d_tmph); (void)hipFree(d_st);
+        DevTemp tmph;
+        if (tmp.alloc((size_t)count * ld * 4) != hipSuccess || tmph.alloc((size_t)count * 4) != hipSuccess)
             return fail(HVX_ERR_DEVICE, "hipMalloc of the upsert staging rows failed");
-        }
-        std::vector<uint32_t> st(count);
-        hipError_t e = hipMemsetAsync(d_tmp, 0, (size_t)count * ld * 4, s);
-        if (e == hipSuccess) e = hipMemcpy2DAsync(d_tmp, (size_t)ld * 4, vectors, (size_t)dim * 4, (size_t)dim * 4, count, hipMemcpyDefault, s);
-        if (e == hipSuccess && bf16) e = launch_round_bf16_inplace(d_tmp, (size_t)count * ld, s); // the index IS the rounded vectors: validation and headers see them
-        DevIndex view = ix->dev;
-        view.vec = d_tmp;
-        if (e == hipSuccess) e = launch_validate_rows(view, count, ix->limit, d_st, d_tmph, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(st.data(), d_st, (size_t)count * 4, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        (void)hipFree(d_st); (void)hipFree(d_tmph);
-        if (e != hipSuccess) { (void)hipFree(d_tmp); return fail(HVX_ERR_DEVICE, "row validation: %s", hipGetErrorString(e)); }
-        for (uint32_t i = 0; i < count; ++i)
-            if (st[i]) { (void)hipFree(d_tmp); return fail((int)st[i], "vector of node %llu is invalid for this metric (status %u)", (unsigned long long)node_ids[i], st[i]); }
+        if (const int rc = stage_rows(ix, vectors, node_ids, count, tmp.as<float>(), tmph.as<float>())) return rc;
         // ids that are neither in the image nor above it cannot be placed (rows ascend with ids)
         const std::vector<uint64_t> &ids = ix->ids_ref();
         uint64_t last = ids.empty() ? 0 : ids.back();
         bool any = !ids.empty();
         for (uint32_t i = 0; i < count; ++i) {
             if (ix->find_slot(node_ids[i]) != kSentinel) continue;
-            if (any && node_ids[i] <= last) { (void)hipFree(d_tmp); return fail(HVX_ERR_UNSUPPORTED, "node %llu lies between the ids of the image: it has no row slot (hydrate the image again)", (unsigned long long)node_ids[i]); }
+            if (any && node_ids[i] <= last) return fail(HVX_ERR_UNSUPPORTED, "node %llu lies between the ids of the image: it has no row slot (hydrate the image again)", (unsigned long long)node_ids[i]);
             last = node_ids[i];
             any = true;
         }
     }
+    float *const d_tmp = tmp.as<float>();
     uint32_t wpath = 0u, wties = 0u; // hvx_index_last_write_path / _tie_overflows: over every id's insert half (the delete half touches neither)
-    auto done = [&](int rc) { (void)hipSetDevice(ix->device); (void)hipFree(d_tmp); ix->last_write_path |= wpath; ix->last_write_tie_overflows = wties; return rc; };
+    auto done = [&](int rc) { (void)hipSetDevice(ix->device); ix->last_write_path |= wpath; ix->last_write_tie_overflows = wties; return rc; };
     ix->last_write_path = 0u;
     ix->last_write_tie_overflows = 0u;
     uint64_t nodes = 0, batches = 0, singles = 0;
@@ -1117,16 +1031,17 @@ extern "C" int hvx_index_upsert_batch(hvx_index *ix, const uint64_t *node_ids, c
             uint16_t lv = 0;
             hipError_t e = bf16 ? launch_pack_bf16(vsrc, const_cast<uint16_t *>(d.vecb) + (size_t)row * d.dim, 1u, d.dim, s)
                                 : hipMemcpyAsync(vdst, vsrc, (size_t)ld * 4, hipMemcpyDeviceToDevice, s);
-            uint32_t *d_one = nullptr;
-            if (e == hipSuccess) e = hipMalloc((void **)&d_one, 4);
-            DevIndex view = d;
-            view.vec = vdst;
-            if (e == hipSuccess) e = launch_validate_rows(view, 1, ix->limit, d_one, const_cast<float *>(d.hdr) + row, s); // (the header of the new vector)
-            if (e == hipSuccess && ix->has_simhash) e = launch_simhash_rows(ix->d_planes_t, vdst, d.dim, d.ld, 1, ix->d_node_hash + row, s);
-            if (e == hipSuccess) e = hipMemcpyAsync(&lv, d.level + row, 2, hipMemcpyDeviceToHost, s);
-            if (e == hipSuccess && ix->d_dead) { hipLaunchKernelGGL(clear_dead_bit_kernel, dim3(1), dim3(1), 0, s, ix->d_dead, row); e = hipGetLastError(); }
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
-            (void)hipFree(d_one);
+            { // (staged and validated above: only the header of the new vector is taken, the status word is not read back)
+                DevTemp one_status;
+                if (e == hipSuccess) e = one_status.alloc(4);
+                DevIndex view = d;
+                view.vec = vdst;
+                if (e == hipSuccess) e = launch_validate_rows(view, 1, ix->limit, one_status.as<uint32_t>(), const_cast<float *>(d.hdr) + row, s);
+                if (e == hipSuccess && ix->has_simhash) e = launch_simhash_rows(ix->d_planes_t, vdst, d.dim, d.ld, 1, ix->d_node_hash + row, s);
+                if (e == hipSuccess) e = hipMemcpyAsync(&lv, d.level + row, 2, hipMemcpyDeviceToHost, s);
+                if (e == hipSuccess && ix->d_dead) { hipLaunchKernelGGL(clear_dead_bit_kernel, dim3(1), dim3(1), 0, s, ix->d_dead, row); e = hipGetLastError(); }
+                if (e == hipSuccess) e = hipStreamSynchronize(s);
+            }
             if (e != hipSuccess) return done(fail(HVX_ERR_DEVICE, "upsert of node %llu: %s", (unsigned long long)node_ids[i], hipGetErrorString(e)));
             { // caches derived from the rows' VECTORS (per-handle |x|^2, the image's bf16 shadow) are rebuilt by their next user
                 std::lock_guard<std::mutex> g(ix->shared->mu);
@@ -1139,11 +1054,8 @@ extern "C" int hvx_index_upsert_batch(hvx_index *ix, const uint64_t *node_ids, c
             ix->n_dead -= 1;
             ix->last_write_path = 0u;
             ix->last_write_tie_overflows = 0u;
-            if ((rc = insert_range(ix, row, 1, &lv, row, &seq, 1u, d.n, &one, bf16 ? vsrc : nullptr))) return done(rc);
-            ix->desc.has_entry = 1;
-            ix->desc.entry_point = ix->ids_ref()[d.entry];
-            ix->desc.max_layer = d.max_layer;
-            ix->publish_view();
+            if ((rc = insert_range(ix, WriteRows{row, 1, 1u, d.n, &lv, row, bf16 ? vsrc : nullptr}, &seq, &one))) return done(rc);
+            publish_write(ix);
             ix->seen_rewrite = ix->shared->rewrite_epoch.fetch_add(1, std::memory_order_acq_rel) + 1;
         }
         wpath |= ix->last_write_path;
@@ -1163,26 +1075,19 @@ extern "C" int hvx_index_link_rows(hvx_index *ix, const uint64_t *from_ids, cons
     HIP_TRY(hipSetDevice(ix->device));
     DevIndex &d = ix->dev;
     if (ix->is_fork) return fail(HVX_ERR_UNSUPPORTED, "rows are linked through the handle that owns the image, not a fork");
-    const uint32_t m = ix->desc.m ? ix->desc.m : 16u;
-    const uint32_t m0 = std::max(ix->desc.m0 ? ix->desc.m0 : 2u * m, 2u * m);
+    const WriteDegrees g = write_degrees(ix->desc, nullptr);
     const bool fused = kernel_fused(d.fkernel);
     const bool bf16 = d.dtype == HVX_BF16;
     const BuildKernels kern = pick_build_kernels(d.metric, fused, bf16);
-    const uint32_t ncmax = std::max(m0, m) + 1u;
-    const uint32_t nk_rows = d.dim_main >> 5;
-    const uint32_t link_ck = std::min<uint32_t>(8u, (nk_rows + 1u) & ~1u);
-    const uint32_t ldp = link_ck * 32u + 32u;
-    const bool wide = std::max(m0, m) > 32u;
-    const WideLinkGeom wgeo = wide ? wide_link_geom(d, m, m0) : WideLinkGeom{};
-    const uint32_t selw = wide ? kSelWide : 32u;
+    const LinkGeom geo = g.wide ? wide_link_geom(d, g.m, g.m0) : link_geom(d, g.m, g.m0);
+    const uint32_t selw = g.selw;
     // one refusal per cause
     if (d.dtype != HVX_F32 && !bf16) return fail(HVX_ERR_UNSUPPORTED, "the link workgroups serve f32 and bf16 rows (this image holds dtype %u)", d.dtype);
-    if (std::max(m0, m) > 64u) return fail(HVX_ERR_UNSUPPORTED, "the link workgroups serve m0 <= 64 (m <= 32)");
-    if (wide && bf16) return fail(HVX_ERR_UNSUPPORTED, "the link workgroups serve bf16 rows with m0 <= 32 (the workgroup kernel for m0 <= 64 reads f32 rows)");
+    if (std::max(g.m0, g.m) > 64u) return fail(HVX_ERR_UNSUPPORTED, "the link workgroups serve m0 <= 64 (m <= 32)");
+    if (g.wide && bf16) return fail(HVX_ERR_UNSUPPORTED, "the link workgroups serve bf16 rows with m0 <= 32 (the workgroup kernel for m0 <= 64 reads f32 rows)");
     if (bf16 && d.dim % 64u != 0u) return fail(HVX_ERR_UNSUPPORTED, "the link workgroups serve bf16 rows with dim %% 64 == 0");
-    if (d.s0 < m0) return fail(HVX_ERR_UNSUPPORTED, "the image's layer-0 rows (%u ids) are narrower than m0 = %u", d.s0, m0);
-    const bool fits = bf16 ? (size_t)(ncmax + 1u) * link_ck * 4u <= (size_t)kLinkPreBf16 * 256u : (size_t)(ncmax + 1u) * link_ck * 8u <= (size_t)kLinkPre * 256u;
-    if (wide ? !wgeo.ok : (!kern.link_wg || kernel_w4(d.fkernel) || ncmax > 33u || nk_rows == 0 || d.dim_main != d.dim || d.ld != d.dim || !fits))
+    if (d.s0 < g.m0) return fail(HVX_ERR_UNSUPPORTED, "the image's layer-0 rows (%u ids) are narrower than m0 = %u", d.s0, g.m0);
+    if (!geo.ok)
         return fail(HVX_ERR_UNSUPPORTED, "the link workgroups serve L2 / cosine under the 256-bit summation trees, dim %% 32 == 0, rows of at most 64 ids");
     std::vector<uint32_t> h_nodes(n_links), h_sel((size_t)n_links * selw, kSentinel), h_cnt(n_links, 1u);
     for (uint32_t i = 0; i < n_links; ++i) {
@@ -1192,16 +1097,13 @@ extern "C" int hvx_index_link_rows(hvx_index *ix, const uint64_t *from_ids, cons
         h_sel[(size_t)i * selw] = t;
     }
     hipStream_t s = ix->stream;
-    uint32_t *d_nodes = nullptr, *d_sel = nullptr, *d_cnt = nullptr, *d_locks = nullptr, *d_err = nullptr;
-    auto release = [&]() {
-        for (void *p : {(void *)d_nodes, (void *)d_sel, (void *)d_cnt, (void *)d_locks, (void *)d_err})
-            if (p) (void)hipFree(p);
-    };
-    auto bail = [&](int rc) { (void)hipStreamSynchronize(s); release(); return rc; };
-    if (hipMalloc((void **)&d_nodes, (size_t)n_links * 4) != hipSuccess || hipMalloc((void **)&d_sel, (size_t)n_links * selw * 4) != hipSuccess ||
-        hipMalloc((void **)&d_cnt, (size_t)n_links * 4) != hipSuccess || hipMalloc((void **)&d_locks, (size_t)d.n * 4) != hipSuccess ||
-        hipMalloc((void **)&d_err, 4) != hipSuccess)
+    DevTemp t_nodes, t_sel, t_cnt, t_locks, t_err; // (released when the call returns; a failed call waits for the stream first)
+    auto bail = [&](int rc) { (void)hipStreamSynchronize(s); return rc; };
+    if (t_nodes.alloc((size_t)n_links * 4) != hipSuccess || t_sel.alloc((size_t)n_links * selw * 4) != hipSuccess ||
+        t_cnt.alloc((size_t)n_links * 4) != hipSuccess || t_locks.alloc((size_t)d.n * 4) != hipSuccess || t_err.alloc(4) != hipSuccess)
         return bail(fail(HVX_ERR_DEVICE, "hipMalloc of the link scratch failed"));
+    uint32_t *const d_nodes = t_nodes.as<uint32_t>(), *const d_sel = t_sel.as<uint32_t>(), *const d_cnt = t_cnt.as<uint32_t>();
+    uint32_t *const d_locks = t_locks.as<uint32_t>(), *const d_err = t_err.as<uint32_t>();
     if (hipMemcpyAsync(d_nodes, h_nodes.data(), (size_t)n_links * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
         hipMemcpyAsync(d_sel, h_sel.data(), h_sel.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
         hipMemcpyAsync(d_cnt, h_cnt.data(), (size_t)n_links * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
@@ -1215,15 +1117,16 @@ extern "C" int hvx_index_link_rows(hvx_index *ix, const uint64_t *from_ids, cons
     ba.layers = 1; // layer 0 only
     ba.sel = d_sel;
     ba.sel_cnt = d_cnt;
-    ba.m = m;
-    ba.m0 = m0;
+    ba.m = g.m;
+    ba.m0 = g.m0;
     ba.err = d_err;
-    ba.ldp = wide ? wgeo.ldp : ldp;
-    ba.ncmax = wide ? wgeo.ncmax : ncmax;
-    ba.link_ck = wide ? wgeo.link_ck : link_ck;
+    ba.ldp = geo.ldp;
+    ba.ncmax = geo.ncmax;
+    ba.link_ck = geo.link_ck;
     ba.selw = selw;
-    const size_t lds = wide ? wgeo.lds : link_lds_bytes(ldp, ncmax);
-    auto launch = [&]() { return wide ? launch_build_link_wide_wg(ba, fused, 1, lds, s) : launch_link_wg(kern.link_wg, ba, 1, lds, s); };
+    auto launch = [&]() {
+        return g.wide ? launch_build_link_wide_wg(ba, fused, 1, geo.lds, s) : launch_step(kern.link_wg, StepGeom{ba.b * 32u, 1u, 256u, geo.lds, 0u, 0u}, ba, s);
+    };
     hipError_t e = hipSuccess;
     if (concurrent) {
         ba.nodes = d_nodes;
@@ -1242,7 +1145,6 @@ extern "C" int hvx_index_link_rows(hvx_index *ix, const uint64_t *from_ids, cons
     uint32_t err = 0;
     if (hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
         return bail(fail(HVX_ERR_DEVICE, "link kernels failed: %s", hipGetErrorString(hipGetLastError())));
-    release();
     if (err) return fail(HVX_ERR_INVARIANT, "a neighbour row overflowed its stride during the link step");
     return HVX_OK;
 }

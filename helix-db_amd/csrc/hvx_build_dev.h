@@ -104,6 +104,15 @@ __device__ __forceinline__ void remove_edge_w(const BuildArgs &a, uint32_t layer
     unlock_row_w(a.locks, owner, lane);
 }
 
+// ---- ONE node at a time, degree limits up to 32 (hvx_build.hip: build_select_seq_kernel / build_link_seq_kernel) ----
+constexpr uint32_t kSeqRow = 35;                 // ids of a link's list (row + the node); wider rows take the one-wavefront kernel
+constexpr uint32_t kSeqRS = 36;                  // stride of a link's matrix: rows 0 .. nc (row nc: the owner's), columns 0 .. nc - 1
+constexpr uint32_t kSeqSelDm = 65 * 64;          // the select's matrix
+constexpr uint32_t kSeqLinkDm = kSeqRS * kSeqRS;
+constexpr uint32_t kSeqLayerDm = kSeqSelDm + 32u * kSeqLinkDm;
+constexpr uint32_t kSeqPairs = 128;              // (row, victim) removals one layer's links can log
+static size_t seq_lds_bytes() { return (size_t)(2 * 32 * kSeqRS + 5 * 32 + 2 * kSeqPairs + 36 + 16 * 128) * 4; } // SeqLds (hvx_build.hip)
+
 using BuildKernel = void (*)(BuildArgs);
 // build_link_wg_kernel over bf16 rows (hvx_build_bf16.hip; hvx_build_link_wg.h), L2 / cosine
 BuildKernel build_link_wg_bf16_kernel(uint32_t metric);
@@ -111,9 +120,7 @@ BuildKernel build_link_wg_bf16_kernel(uint32_t metric);
 // ---- degree limits above 32 (hvx_build_wide.hip): Mmax = max(m0, m) <= 64 ----
 constexpr uint32_t kCandWide = 128; // candidates kept per layer and node (2 * Mmax <= 128)
 constexpr uint32_t kSelWide = 64;   // selected neighbours per layer and node
-struct WideLinkGeom { uint32_t ldp, ncmax, link_ck; size_t lds; bool ok; };
-// geometry of build_link_wide_wg_kernel for this image; ok = false where it has no build (the one-wavefront kernel links instead)
-WideLinkGeom wide_link_geom(const DevIndex &d, uint32_t m, uint32_t m0);
+// (geometry of build_link_wide_wg_kernel for an image: wide_link_geom, hvx_build_plan.h)
 hipError_t launch_build_select_wide(const BuildArgs &a, bool fused, bool bf16, dim3 grid, hipStream_t s);
 hipError_t launch_build_link_wide(const BuildArgs &a, bool fused, bool bf16, uint32_t nodes, hipStream_t s);
 hipError_t launch_build_link_wide_wg(const BuildArgs &a, bool fused, uint32_t layers, size_t lds, hipStream_t s);

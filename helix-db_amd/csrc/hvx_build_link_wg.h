@@ -6,7 +6,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "hvx_build_dev.h"
+#include "hvx_build_plan.h"
 
 namespace hvx {
 
@@ -26,7 +26,7 @@ namespace hvx {
 // (mod.rs:809-856) is a walk over 64-bit masks: candidate i is diverse iff P[i] & kept == 0.  Same decisions as the lazy
 // evaluation, bit for bit.
 constexpr int kLinkTasks = 18; // wave-steps of 8 pairs per wavefront: 4 x 18 x 8 >= 561 pairs of 33 candidates + owner
-constexpr int kLinkPre = 9, kLinkPreBf16 = 5; // 16-byte pieces of the next column block a thread holds in registers: f32 / bf16 rows
+// (kLinkPre / kLinkPreBf16, link_pairs_max and link_lds_bytes: hvx_build_plan.h, next to the predicate that decides where the kernel serves)
 
 struct LinkLds {
     float *rows;              // [ncmax + 1][ldp]: this column block of the candidate rows (row order of the neighbour row), then the owner's
@@ -40,7 +40,6 @@ struct LinkLds {
     uint32_t *sh;             // [8] nc, prune, present, overflow
     unsigned char *pa, *pb;   // [pairs] the two rows of pair p
 };
-__device__ __host__ __forceinline__ size_t link_pairs_max(uint32_t ncmax) { return (size_t)(ncmax + 1u) * ncmax / 2u; }
 __device__ __forceinline__ LinkLds carve_link(char *smem, uint32_t ldp, uint32_t ncmax) {
     LinkLds L;
     L.rows = reinterpret_cast<float *>(smem);
@@ -57,11 +56,6 @@ __device__ __forceinline__ LinkLds carve_link(char *smem, uint32_t ldp, uint32_t
     L.pb = reinterpret_cast<unsigned char *>(p);
     return L;
 }
-inline size_t link_lds_bytes(uint32_t ldp, uint32_t ncmax) {
-    return (size_t)(ncmax + 1u) * ldp * 4u + 512u + (size_t)(ncmax + 1u) * (ncmax + 1u) * 4u + 5u * 256u + 32u +
-           2u * ((link_pairs_max(ncmax) + 15u) & ~(size_t)15u);
-}
-
 
 template <uint32_t METRIC, bool FUSED, bool BF> __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void build_link_wg_kernel(BuildArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];

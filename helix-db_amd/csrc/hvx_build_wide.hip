@@ -22,7 +22,7 @@
 
 #include <algorithm>
 
-#include "hvx_build_dev.h"
+#include "hvx_build_plan.h"
 
 using namespace hvx;
 
@@ -214,9 +214,7 @@ template <uint32_t METRIC, bool FUSED, bool BF> __global__ __launch_bounds__(64)
 // thread in flight: 66 rows x 32 float4 / 1 024 threads) compile without scratch, blocks of 256 floats (5 float4) spill 14 dwords.
 // 66 rows x 160 floats = 42 KB + a 66 x 66 distance matrix (17 KB) + lists = 68 KB of LDS, one or two workgroups per CU (the second
 // only where the first has shrunk to its tail wavefront: 16 + 16 wavefronts of 128 registers do not fit a CU).
-constexpr int kWideTasks = 17; // wave-steps of 8 pairs per wavefront
-constexpr int kWidePre = 3;    // float4 a thread carries for the next block
-constexpr uint32_t kWideWaves = 16;
+// (kWideTasks = 17, kWidePre = 3 float4 in flight, kWideWaves = 16, the LDS size and where the kernel serves: wide_link_geom, hvx_build_plan.h)
 
 struct WideLinkLds {
     float *rows;              // [ncmax + 1][ldp]: this column block of the candidate rows (list order), then the owner's
@@ -230,7 +228,6 @@ struct WideLinkLds {
     uint32_t *sh;             // [8] nc, prune, present, overflow
     unsigned char *pa, *pb;   // [pairs] the two rows of pair p
 };
-__device__ __host__ __forceinline__ size_t wide_pairs_max(uint32_t ncmax) { return (((size_t)(ncmax + 1u) * ncmax / 2u) + 15u) & ~(size_t)15u; }
 __device__ __forceinline__ WideLinkLds carve_wide_link(char *smem, uint32_t ldp, uint32_t ncmax) {
     WideLinkLds L;
     L.rows = reinterpret_cast<float *>(smem);
@@ -246,9 +243,6 @@ __device__ __forceinline__ WideLinkLds carve_wide_link(char *smem, uint32_t ldp,
     L.pa = reinterpret_cast<unsigned char *>(p); p += wide_pairs_max(ncmax);
     L.pb = reinterpret_cast<unsigned char *>(p);
     return L;
-}
-static size_t wide_link_lds_bytes(uint32_t ldp, uint32_t ncmax) {
-    return (size_t)(ncmax + 1u) * ldp * 4u + 128u * 16u + (size_t)(ncmax + 1u) * (ncmax + 1u) * 4u + 4u * 512u + 256u + 32u + 2u * wide_pairs_max(ncmax);
 }
 
 template <uint32_t METRIC, bool FUSED> __global__ __launch_bounds__(1024) void build_link_wide_wg_kernel(BuildArgs a) {
@@ -487,21 +481,6 @@ static WideKernels pick_wide_kernels(uint32_t metric, bool fused, bool bf16) {
     if (metric == kL2) return fused ? wide_kernels_of<kL2, true>() : wide_kernels_of<kL2, false>();
     if (metric == kCosine) return fused ? wide_kernels_of<kCosine, true>() : wide_kernels_of<kCosine, false>();
     return fused ? wide_kernels_of<kL1, true>() : wide_kernels_of<kL1, false>();
-}
-
-WideLinkGeom wide_link_geom(const DevIndex &d, uint32_t m, uint32_t m0) {
-    WideLinkGeom g{};
-    g.ncmax = std::max(m0, m) + 1u;
-    const uint32_t nk_rows = d.dim_main >> 5;
-    g.link_ck = std::min<uint32_t>(4u, (nk_rows + 1u) & ~1u);
-    g.ldp = g.link_ck * 32u + 32u;
-    g.lds = wide_link_lds_bytes(g.ldp, g.ncmax);
-    // f32 rows without a scalar tail (dim % 32 == 0, no padding), L2 / cosine, the 32-lane summation trees, <= 65 candidates
-    // (2 145 pairs = 16 wavefronts x 17 steps x 8; a column block of 66 rows = 3 float4 per thread)
-    g.ok = d.dtype == HVX_F32 && (d.metric == kL2 || d.metric == kCosine) && !kernel_w4(d.fkernel) && g.ncmax <= 65u && nk_rows > 0 && d.dim_main == d.dim &&
-           d.ld == d.dim && d.s0 <= 64u && d.su <= 64u && (size_t)(g.ncmax + 1u) * g.link_ck * 8u <= (size_t)kWidePre * 1024u &&
-           (size_t)(g.ncmax + 1u) * g.ncmax / 2u <= (size_t)kWideWaves * kWideTasks * 8u;
-    return g;
 }
 
 hipError_t launch_build_select_wide(const BuildArgs &a, bool fused, bool bf16, dim3 grid, hipStream_t s) {

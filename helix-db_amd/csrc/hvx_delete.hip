@@ -42,6 +42,7 @@
 
 #include "hvx_host.h"
 #include "hvx_graph_dev.h"
+#include "hvx_build_plan.h"
 #include "hvx_toplist.h"
 
 using namespace hvx;
@@ -638,8 +639,8 @@ extern "C" int hvx_index_delete_batch(hvx_index *ix, const uint64_t *node_ids, u
     if (d.dtype != HVX_F32 && d.dtype != HVX_BF16)
         return fail(HVX_ERR_UNSUPPORTED, "nodes are deleted from f32 and bf16 images (fp8 rows: import the changed graph afterwards)");
     const bool bf16 = d.dtype == HVX_BF16;
-    const uint32_t m = ix->desc.m ? ix->desc.m : 16u;
-    const uint32_t m0 = std::max(ix->desc.m0 ? ix->desc.m0 : 2u * m, 2u * m);
+    const WriteDegrees deg = write_degrees(ix->desc, nullptr);
+    const uint32_t m = deg.m, m0 = deg.m0;
     if (m0 > kDelTop || m > kDelTop || d.s0 > 64u || d.su > 64u || d.s0 < m0 || d.su < m)
         return fail(HVX_ERR_UNSUPPORTED, "device delete serves degree limits <= 64 on rows at least that wide and at most 64 ids (m %u m0 %u strides %u / %u)", m, m0, d.su, d.s0);
     const auto t0 = std::chrono::steady_clock::now();

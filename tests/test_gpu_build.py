@@ -445,3 +445,72 @@ def test_batched_inserts_keep_the_graph_invariants_and_serve_every_search_path(o
     lane.refresh()
     lid, _, _, _ = lane.search_batch(q, hv.SearchParams(10).with_ef(100))
     assert lid.tolist() == gid.tolist()
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Every step kind plan_write_batch (csrc/hvx_build_plan.h) can return, on a small image: hvx_index_last_write_path equals the bits
+# of the plan's recorded line for that input (tests/build_plan_table.txt, pinned on the host by tests/test_build_plan.py).
+# The wide one-wavefront link of batches >= 1 024 nodes needs 65 536 rows: the table and bench.py hold it.
+# name, dtype, dim, m, m0, row strides (import_index: multiples of 32 / 16 ids), link_mode, nodes per batch (1: one-node mode)
+PLAN_KINDS = [("narrow batched", 0, 64, 8, 16, 32, 16, 0, 100),
+              ("narrow one-node eager", 0, 64, 8, 16, 32, 16, 0, 1),
+              ("narrow link_mode 1", 0, 64, 8, 16, 32, 16, 1, 1),
+              ("wide batched", 0, 64, 32, 64, 64, 32, 0, 50),
+              ("wide one-node eager", 0, 64, 32, 64, 64, 32, 0, 1),
+              ("wide link_mode 1", 0, 64, 32, 64, 64, 32, 1, 1),
+              ("bf16 narrow one-node", 1, 128, 8, 16, 32, 16, 0, 1)]
+_PLAN_ORACLE = {}
+
+
+def _plan_inputs(orc, dtype, dim, m, m0):
+    """400 clustered rows and the oracle's sequential graph over them (bf16 images: over the rounded rows); once per shape, read only."""
+    key = (dtype, dim, m, m0)
+    if key not in _PLAN_ORACLE:
+        n = 400
+        data, _, _ = fx.clustered_rows(dim, n, seed=4100 + dim + m)
+        lv = fx.draw_levels(n, m, seed=n + m)
+        ids = np.arange(n, dtype=np.uint64) * 3 + 7
+        oix = oracle_build(orc, fx.round_bf16(data) if dtype == 1 else data, 1, lv, m, m0, 64, ids)
+        _PLAN_ORACLE[key] = (data, lv, ids, oix.export())
+    return _PLAN_ORACLE[key]
+
+
+@pytest.mark.parametrize("name,dtype,dim,m,m0,s0,su,link_mode,bsz", PLAN_KINDS, ids=[k[0] for k in PLAN_KINDS])
+def test_every_step_kind_of_the_write_plan_reports_the_tables_path_bits(orc, hv, name, dtype, dim, m, m0, s0, su, link_mode, bsz):
+    """One-node mode: a sequential build of the 400 rows -- the path word equals the plan's, the audit is clean and the rows equal the
+    oracle's row for row.  Batched: the first 300 rows built one node at a time, the other 100 (layer 0 only: no promotion) appended
+    with batch_divisor 3 -- ONE batch of 100 nodes (limits above 32 halve the fraction: two of 50) --, so the call's path word is
+    that batch's plan; the audit is clean."""
+    import re
+    from test_build_plan import plan_table
+    n, n0, efc = 400, 300, 64
+    data, lv, ids, ex = _plan_inputs(orc, dtype, dim, m, m0)
+    mode = hv.BUILD_ONE_NODE if bsz == 1 else hv.BUILD_BATCHED
+    line = plan_table()[f"W dt={dtype} me=1 fk=3 dim={dim} ld={dim} m={m} m0={m0} s0={s0} su={su} lm={link_mode} mode={mode} bsz={bsz} promotes=0 layers=3"]
+    want = int(re.search(r"path=0x([0-9a-f]+)$", line).group(1), 16)
+    if bsz == 1:
+        gix, st = hv.ValidatedVectorReadIndex.build(dim=dim, metric=1, node_ids=ids, vectors=data, levels=lv, m=m, m0=m0, ef_construction=efc,
+                                                    sequential=True, link_mode=link_mode, dtype=dtype)
+        assert st["nodes"] == n and st["batches"] == n - 1
+    else:
+        gix, _ = hv.ValidatedVectorReadIndex.build(dim=dim, metric=1, node_ids=ids[:n0], vectors=data[:n0], levels=lv[:n0], m=m, m0=m0,
+                                                   ef_construction=efc, sequential=True, reserve_rows=n - n0, dtype=dtype)
+        st = gix.insert_batch(ids[n0:], data[n0:], np.zeros(n - n0, np.uint16), ef_construction=efc, batch_divisor=3, sequential=hv.BUILD_BATCHED,
+                              link_mode=link_mode)
+        assert st["nodes"] == n - n0 and st["batches"] == (n - n0) // bsz and st["single_node_batches"] == 0, st
+    print(f"{name}: plan line `{line}`, path word 0x{gix.last_write_path():x}")
+    assert gix.last_write_path() == want, (name, hex(gix.last_write_path()), line)
+    a = gix.audit_graph()
+    for key in ("asymmetric_edges_l0", "asymmetric_edges_up", "unsorted_entries", "self_loops", "out_of_range_ids", "holes", "level_violations",
+                "degree_overflow_rows", "unreachable_l0"):
+        assert a[key] == 0, (name, key, a)
+    assert a["nodes"] == n and a["max_degree_l0"] <= m0 and a["max_degree_up"] <= m
+    if bsz == 1:
+        g = gix.export_graph()
+        assert g["entry_point"] == ex["entry_point"] and g["max_layer"] == ex["max_layer"] and g["level"].tolist() == ex["level"].tolist()
+        gl0, gup = rows_of(g, n)
+        ol0, oup = rows_of(ex, n)
+        bad = [i for i in range(n) if gl0[i] != ol0[i]]
+        assert not bad, f"{name}: {len(bad)} layer-0 rows differ, first {bad[:5]}"
+        assert gup == oup
+    gix.close()
