@@ -955,8 +955,15 @@ int hvx_index_insert_batch(hvx_index *, const uint64_t *node_ids /*[count]*/, co
  * hvx_index_insert_batch: owner handle only, visible_seq + 1 per call that deleted something, forks adopt with hvx_index_refresh.
  * Its id comes back through hvx_index_upsert_batch (into the same slot), not through hvx_index_insert_batch (ids ascend).
  * f32 and bf16 images (bf16: relinked on the rounded vectors), degree limits <= 64 on rows of at most 64 ids; fp8 images are refused.
- * HVX_ERR_UNSUPPORTED when more than 4 096 rows of one layer hold a node or their joint
- * neighbourhood exceeds 16 384 rows (after such a failure the image is partially relinked: discard the handle).
+ * Three limits per deleted node and layer, each refused with HVX_ERR_UNSUPPORTED and its own text in hvx_last_error:
+ *   more than 4 096 rows hold the node                                       "more than 4096 rows hold one node on a layer"
+ *   more than 4 096 relink sources (those rows + the node's own out-neighbours,
+ *   which relink whether or not they hold it: an asymmetric graph can have
+ *   4 096 holders or fewer and still more sources)                           "more than 4096 relink sources on a layer"
+ *   more than 16 384 relink candidates (the sources and everything their
+ *   rows hold, the node excluded)                                             "more than 16384 relink candidates on a layer"
+ * Exactly 4 096 / 4 096 / 16 384 are served (tests/test_gpu_delete_hubs.py).  After such a failure the image is partially relinked
+ * (nodes earlier in the batch are deleted, later ones are not): discard the handle and hydrate again.
  */
 typedef struct hvx_delete_stats {
     uint32_t requested, deleted, missing; /* ids given / nodes removed / ids that were not (or no longer) in the image */
