@@ -59,12 +59,7 @@ template <uint32_t METRIC, bool FUSED, bool BF> __global__ __launch_bounds__(256
             const float d = pair_distance<METRIC, FUSED, BF>(ix, ni, nj, j);
             if (j == 0) { st_agent(gl + i * rw + jj, d); st_agent(gl + jj * rw + i, d); }
         }
-        stores_done(); // the stores have been acknowledged before the ticket is taken
-        __syncthreads();
-        if (tid == 0) s_last = __hip_atomic_fetch_add(a.tick + L, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == G ? 1u : 0u;
-        __syncthreads();
-        last = s_last != 0u;
-        if (last && tid == 0) st_agent(a.tick + L, 0u);
+        last = last_workgroup(a.tick, L, G, &s_last, true); // (hvx_handoff.h; the ticket goes back to zero)
     }
     if (!last || wave != 0u) return;
     uint32_t ns = hyd;
@@ -163,36 +158,11 @@ template <uint32_t METRIC, bool FUSED, bool BF> __global__ __launch_bounds__(102
     __syncthreads();
     const uint32_t total = S.pbase[64];
     float *gl = a.gdm + geo.link_off(L, 0u);
-    bool last;
-    { // (the ticket is taken even when no list needs a matrix: the last workgroup rewrites rows the others are still reading their lists from)
-        const int j = (int)(lane & 7u);
-        for (uint32_t p = g * 128u + (tid >> 3); p < total; p += G * 128u) {
-            uint32_t lo = 0u, hi = ns; // the link t with pbase[t] <= p < pbase[t + 1]
-            while (hi - lo > 1u) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (S.pbase[mid] <= p) lo = mid; else hi = mid;
-            }
-            const uint32_t t = lo;
-            uint32_t i, jj;
-            pair_of(p - S.pbase[t], i, jj); // 0 <= jj < i <= nc
-            const uint32_t *rc = S.rcur + t * kWideSeqLS;
-            const uint32_t nc = S.rdeg[t];
-            const uint32_t node_i = i < nc ? rc[i] : S.to[t], node_j = rc[jj];
-            const float d = pair_distance<METRIC, FUSED, BF>(ix, node_i, node_j, j);
-            if (j == 0) {
-                float *out = gl + (size_t)t * geo.link_dm;
-                st_agent(out + i * kWideSeqRS + jj, d);
-                if (i < nc) st_agent(out + jj * kWideSeqRS + i, d);
-            }
-        }
-        stores_done();
-        __syncthreads();
-        if (tid == 0) s_last = __hip_atomic_fetch_add(a.tick + a.layers + L, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == G ? 1u : 0u;
-        __syncthreads();
-        last = s_last != 0u;
-        if (last && tid == 0) st_agent(a.tick + a.layers + L, 0u);
-    }
-    if (!last) return;
+    pair_sweep<METRIC, FUSED, BF, 1024>(ix, S.pbase, ns, total, g, G, [&](uint32_t t) __attribute__((always_inline)) {
+        return PairTask{S.rcur + t * kWideSeqLS, S.rdeg[t], S.to[t], gl + (size_t)t * geo.link_dm, kWideSeqRS};
+    });
+    // (the ticket is taken even when no list needs a matrix: the last workgroup rewrites rows the others are still reading their lists from)
+    if (!last_workgroup(a.tick, a.layers + L, G, &s_last, true)) return;
     // ---- the last workgroup: every link replayed on its list as found (sixteen at a time) ...
     uint32_t *W2 = S.wsc + wave * kWide2Words;
     const uint32_t *kept = W2 + kWide2Kept;

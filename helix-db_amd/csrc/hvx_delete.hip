@@ -502,45 +502,13 @@ template <uint32_t METRIC, bool FUSED, bool BF, bool WIDE> __global__ __launch_b
     __syncthreads();
     const uint32_t total = S.pbase[kDelTop + 1u];
     float *gl = a.gdm + (size_t)L * fuse_layer_dm<T>();
-    bool last;
-    { // (the ticket is taken even when nothing needs a matrix: the last workgroup rewrites rows the others are still reading their tasks from)
-        const int j = (int)(lane & 7u);
-        for (uint32_t p = g * (kFuseWaves * 8u) + (tid >> 3); p < total; p += G * (kFuseWaves * 8u)) {
-            uint32_t lo = 0u, hi = nadd + 1u; // the task t with pbase[t] <= p < pbase[t + 1]
-            while (hi - lo > 1u) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (S.pbase[mid] <= p) lo = mid; else hi = mid;
-            }
-            const uint32_t t = lo, q = p - S.pbase[t];
-            // q = i (i - 1) / 2 + jj, 0 <= jj < i <= nc
-            uint32_t i = (uint32_t)((1.0f + sqrtf(1.0f + 8.0f * (float)q)) * 0.5f);
-            while (i * (i - 1u) / 2u > q) --i;
-            while ((i + 1u) * i / 2u <= q) ++i;
-            const uint32_t jj = q - i * (i - 1u) / 2u;
-            uint32_t node_i, node_j, nc, st;
-            float *out;
-            if (t == 0u) {
-                nc = ncur; st = T::OWN_RW; out = gl;
-                node_i = i < nc ? S.cur[i] : nb; node_j = S.cur[jj];
-            } else {
-                const uint32_t *rc = S.rcur + (t - 1u) * T::RS;
-                nc = S.rdeg[t - 1u]; st = T::RECIP_RW; out = gl + fuse_own_dm<T>() + (size_t)(t - 1u) * fuse_recip_dm<T>();
-                node_i = i < nc ? rc[i] : S.addl[t - 1u]; node_j = rc[jj];
-            }
-            const float d = pair_distance<METRIC, FUSED, BF>(ix, node_i, node_j, j);
-            if (j == 0) {
-                st_agent(out + i * st + jj, d);
-                if (i < nc) st_agent(out + jj * st + i, d);
-            }
-        }
-        stores_done(); // the stores have been acknowledged before the ticket is taken
-        __syncthreads();
-        if (tid == 0) s_last = __hip_atomic_fetch_add(a.tick + L, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == G ? 1u : 0u;
-        __syncthreads();
-        last = s_last != 0u;
-        if (last && tid == 0) st_agent(a.tick + L, 0u); // (the next launch starts from zero)
-    }
-    if (!last) return;
+    pair_sweep<METRIC, FUSED, BF, kFuseWaves * 64u>(ix, S.pbase, nadd + 1u, total, g, G, [&](uint32_t t) __attribute__((always_inline)) {
+        if (t == 0u) return PairTask{S.cur, ncur, nb, gl, T::OWN_RW}; // the source's own prune, then candidate t - 1's
+        return PairTask{S.rcur + (t - 1u) * T::RS, S.rdeg[t - 1u], S.addl[t - 1u], gl + fuse_own_dm<T>() + (size_t)(t - 1u) * fuse_recip_dm<T>(), T::RECIP_RW};
+    });
+    // (the ticket is taken even when nothing needs a matrix: the last workgroup rewrites rows the others are still reading their tasks from;
+    // it is written back to zero: the next launch starts from there)
+    if (!last_workgroup(a.tick, L, G, &s_last, true)) return;
     // ---- the last workgroup.  The reciprocal prunes do not depend on the source's (only whether they are APPLIED does): wavefront 0
     // replays the source's prune while wavefronts 1 .. 15 replay the candidates' lists, then the rows of the candidates that stayed go out
     bool bad = false;

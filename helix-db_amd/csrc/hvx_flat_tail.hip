@@ -29,6 +29,7 @@
 #include <algorithm>
 
 #include "hvx_toplist.h"
+#include "hvx_handoff.h"
 #include "hvx_flat_mfma.h"
 #include "hvx_host.h"
 
@@ -37,8 +38,6 @@ namespace hvx {
 namespace {
 
 typedef float f2 __attribute__((ext_vector_type(2)));
-template <typename T> __device__ __forceinline__ T ld_agent(const T *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-template <typename T> __device__ __forceinline__ void st_agent(T *p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 constexpr int kTailR = 16;                  // scores per thread
 constexpr int kTailSlice = kTailR * 256;    // 4 096 scores per workgroup
@@ -253,15 +252,8 @@ __global__ __launch_bounds__(256) void flat_exact_tail_kernel(TailArgs a) {
             st_agent(a.part_row + at, l.id);
         }
     }
-    // No device-scope fence here: an agent-scope release / acquire pair is an L2 write-back and an L2 INVALIDATE on this part (one L2 per
-    // XCD), and hundreds of short workgroups doing that to the L2 their neighbours are streaming rows through cost more than the scan
-    // (first build: 200 us at 100 000 x 32).  The lists are written with device-scope (write-through) stores and read with device-scope
-    // loads; the stores have been acknowledged (vscnt = 0, workgroup-scope release) before the ticket is taken.
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // (a workgroup-scope release fence does not wait for global stores outside threadgroup-split mode)
-    __syncthreads();
-    if (tid == 0) s_last = __hip_atomic_fetch_add(&a.done[q], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == a.slices ? 1u : 0u;
-    __syncthreads();
-    if (!s_last) return;
+    // the last workgroup of the query to get here merges the slices' lists (no device-scope fence: hvx_handoff.h)
+    if (!last_workgroup(a.done, q, a.slices, &s_last, false)) return;
     const uint32_t per_query = a.slices * k;
     TopList l;
     l.init();

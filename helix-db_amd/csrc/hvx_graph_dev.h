@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "hvx_device.h"
+#include "hvx_handoff.h"
 
 namespace hvx {
 
@@ -209,14 +210,9 @@ __device__ __forceinline__ float pair_distance(const DevIndex &ix, uint32_t ni, 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Eager prunes (round 6): a prune's distance matrix is evaluated up front by many workgroups (one 8-lane group per pair), written to HBM
 // with device-scope stores, and ONE wavefront of the last workgroup to deliver replays select_diverse + backfill from registers.  Shared
-// by the delete steps (hvx_delete.hip) and the sequential insert's select / link steps (hvx_build.hip).
+// by the delete steps (hvx_delete.hip) and the sequential insert's select / link steps (hvx_build.hip, hvx_build_wide_seq.hip).
 // ---------------------------------------------------------------------------------------------------------------------------------
-template <typename T> __device__ __forceinline__ T ld_agent(const T *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-template <typename T> __device__ __forceinline__ void st_agent(T *p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// every global store of this wavefront has been performed.  A workgroup-scope release fence does NOT wait for them (all wavefronts of a
-// workgroup sit behind one vector cache: the compiler omits vmcnt(0) outside threadgroup-split mode), and an agent-scope one writes back
-// and invalidates the XCD's L2 -- so the "last workgroup" tickets wait explicitly before the barrier in front of the ticket
-__device__ __forceinline__ void stores_done() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+// (st_agent / ld_agent, stores_done() and the last workgroup's ticket: hvx_handoff.h)
 __device__ __forceinline__ void lds_order() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); } // one wavefront's LDS writes before its next reads
 struct WaveScratch { uint32_t *ord, *kept; }; // [64] each, per wavefront
 
@@ -226,6 +222,34 @@ __device__ __forceinline__ void pair_of(uint32_t q, uint32_t &i, uint32_t &j) {
     while (i * (i - 1u) / 2u > q) --i;
     while ((i + 1u) * i / 2u <= q) ++i;
     j = q - i * (i - 1u) / 2u;
+}
+
+// The pairs of a step's prunes, spread over the workgroups of a layer (the eager link steps of hvx_build.hip and hvx_build_wide_seq.hip,
+// delete_step_fused_kernel): task t owns pair numbers pbase[t] .. pbase[t + 1) (`total` in all), workgroup g of G takes every G-th run
+// of THREADS / 8 pairs, one 8-lane group per pair (THREADS = the kernel's workgroup size, its __launch_bounds__).  task(t) names the
+// prune: its nc ids, the owner (index nc, whose row has no column of its own) and its matrix, rs floats per row.
+struct PairTask { const uint32_t *ids; uint32_t nc, owner; float *out; uint32_t rs; };
+template <uint32_t METRIC, bool FUSED, bool BF, uint32_t THREADS, typename Task>
+__device__ __forceinline__ void pair_sweep(const DevIndex &ix, const uint32_t *pbase, uint32_t ntasks, uint32_t total, uint32_t g, uint32_t G, Task task) {
+    static_assert(THREADS % 64u == 0u, "whole wavefronts");
+    constexpr uint32_t per = THREADS / 8u;
+    const uint32_t tid = threadIdx.x;
+    const int j = (int)(tid & 7u);
+    for (uint32_t p = g * per + (tid >> 3); p < total; p += G * per) {
+        uint32_t lo = 0u, hi = ntasks; // the task t with pbase[t] <= p < pbase[t + 1]
+        while (hi - lo > 1u) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (pbase[mid] <= p) lo = mid; else hi = mid;
+        }
+        const PairTask k = task(lo);
+        uint32_t i, jj;
+        pair_of(p - pbase[lo], i, jj); // 0 <= jj < i <= nc
+        const float d = pair_distance<METRIC, FUSED, BF>(ix, i < k.nc ? k.ids[i] : k.owner, k.ids[jj], j);
+        if (j == 0) {
+            st_agent(k.out + i * k.rs + jj, d);
+            if (i < k.nc) st_agent(k.out + jj * k.rs + i, d);
+        }
+    }
 }
 
 // select_diverse + backfill (mod.rs:809-856) over a finished matrix, by ONE wavefront, without LDS: lane c reads ROW c of the matrix

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "hvx_toplist.h"
+#include "hvx_handoff.h"
 #include "hvx_host.h"
 
 namespace {
@@ -66,9 +67,7 @@ constexpr int load_group(int nl) {
         if (nl % g == 0) return g;
     return 1;
 }
-// the slices' lists, the flags and the counters cross workgroups that may sit on different XCDs (one L2 each): device-scope accesses
-template <typename T> __device__ __forceinline__ T ld_agent(const T *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-template <typename T> __device__ __forceinline__ void st_agent(T *p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// (the slices' lists, the flags and the counters cross workgroups that may sit on different XCDs, one L2 each: st_agent / ld_agent)
 
 template <uint32_t METRIC> __device__ __forceinline__ void fma_chunk_pk(Acc &acc, const float4 qq, const float4 xv) {
     const f2 ql = {qq.x, qq.y}, qh = {qq.z, qq.w}, xl = {xv.x, xv.y}, xh = {xv.z, xv.w};
@@ -343,16 +342,8 @@ __global__ __launch_bounds__(256) void restricted_direct_kernel(DirectArgs a) {
             }
         }
     }
-    // the last workgroup of the tile to get here merges the slices' lists
-    // No device-scope fence here: an agent-scope release / acquire pair is an L2 write-back and an L2 INVALIDATE on this part (one L2 per
-    // XCD), and hundreds of short workgroups doing that to the L2 their neighbours are streaming rows through cost more than the scan
-    // (first build: 200 us at 100 000 x 32).  The lists are written with device-scope (write-through) stores and read with device-scope
-    // loads; the stores have been acknowledged (vscnt = 0, workgroup-scope release) before the ticket is taken.
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // (a workgroup-scope release fence does not wait for global stores outside threadgroup-split mode)
-    __syncthreads();
-    if (tid == 0) s_last = __hip_atomic_fetch_add(&a.done[tile], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == a.slices ? 1u : 0u;
-    __syncthreads();
-    if (!s_last) return;
+    // the last workgroup of the tile to get here merges the slices' lists (no device-scope fence: hvx_handoff.h)
+    if (!last_workgroup(a.done, tile, a.slices, &s_last, false)) return;
     const uint32_t per_query = a.slices * a.k;
     if constexpr (R > 1) {
         // every wavefront merges the lists of slices wave, wave + 4, ...: the first fills its registers as it is, the others are read a

@@ -29,10 +29,10 @@ def wide_inputs(n, dim, metric, lm):
     return rng, data, ids, lv
 
 
-def full_rows(ex, n):
-    """(layer-0 rows with M0 ids, upper rows with M ids, upper rows) of an export"""
+def full_rows(ex, n, m=M, m0=M0):
+    """(layer-0 rows with m0 ids, upper rows with m ids, upper rows) of an export"""
     l0, up = rows_of(ex, n)
-    return sum(len(r) == M0 for r in l0), sum(len(r) == M for r in up), len(up)
+    return sum(len(r) == m0 for r in l0), sum(len(r) == m for r in up), len(up)
 
 
 def assert_rows_equal(g, ex, n):

@@ -30,14 +30,14 @@ def hv():
 _ORACLE = {}
 
 
-def oracle_of(orc, n, dim, metric, efc, lm):
+def oracle_of(orc, n, dim, metric, efc, lm, m=M, m0=M0):
     """The oracle's sequential build of a shape (once per module; nobody changes it) and, counted on its exports before and after each
     insert, the inserts in which two of the new node's linked neighbours (an id in the node's new row, or an id whose row now holds the
     node) lose their mutual layer-0 edge."""
-    key = (n, dim, metric, efc, lm)
+    key = (n, dim, metric, efc, lm, m, m0)
     if key not in _ORACLE:
         rng, data, ids, lv = wide_inputs(n, dim, metric, lm)
-        oix = orc.Index(dim, metric, kernel=orc.K_AVX_FMA, m=M, m0=M0, ef_construction=efc)
+        oix = orc.Index(dim, metric, kernel=orc.K_AVX_FMA, m=m, m0=m0, ef_construction=efc)
         before, cross = {}, 0
         for i in range(n):
             assert oix.insert(int(ids[i]), data[i], int(lv[i])) == orc.OK
